@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- edges/sec of the equivariant message-passing forward (HamGNNConvE3 + HamGNNPlusPlusOut) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload sio2_10k|si512|mos2_1200|si2|uni8] [--irreps A|B]
+    python bench.py --gpus N --steps K --warmup W [--workload sio2_10k|si512|mos2_1200|si2|uni8] [--irreps A|B] [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 A "step" is ONE inference forward of the whole hot path over one synthetic periodic crystal already resident in HBM:
@@ -9,11 +9,14 @@ backbone (embedding + num_layers x (ConvBlockE3 + PairInteractionBlock)) + pair 
 add_H0, no SOC), random-init weights (seed 666), fp32.  value = directed edges of the crystal * steps / time, whole job.
 For N > 1 the undirected pairs are sharded over the ranks (hamgnn_amd/parallel.py) with one RCCL all-reduce of the node
 aggregates per layer; the crystal (total work) is fixed => "scaling": "strong".
-Prints ONE JSON line (rank 0) incl. `accuracy` (max|H - H_oracle| / max|H_oracle| and MAE of this model on a bounded sub-crystal, fp64 oracle
-in a child process), `compile_s` (host planner + upload), for N > 1 `per_rank` (edges, edge-kernel / all-reduce / other ms per step of every
-rank) and `ranks_seen`, `roofline` for the dominant kernel (the fused MessagePackBlock launches: hg_tp_is, or
-hg_tp_fused on the fallback path; timed live with HIP events on the launch stream inside the timed region) and `cpu_baseline` (the oracle = unfused pure-torch port of the reference path,
-timed on the host cores over a bounded sample of the same workload; rank 0, N=1 only).
+Prints ONE JSON line (rank 0): `value`, `ms_per_step` (wall time of the K timed steps / K), `ms_per_step_median` (HIP events at the step
+boundaries), `compile_s` (host planner + upload), the configuration.  A plain run does nothing else: set-up, W warm-up steps, K timed steps,
+the line.  `--full` adds what takes work of its own: `accuracy` (max|H - H_oracle| / max|H_oracle| and MAE of this model on a bounded sub-crystal,
+fp64 oracle in a child process), for N > 1 `per_rank` (edges, edge-kernel / all-reduce / other ms per step of every rank), `ranks_seen` and
+`sharded_check`, `roofline` for the dominant kernel (the fused MessagePackBlock launches: hg_tp_is, or hg_tp_fused on the fallback path; timed
+live with HIP events on the launch stream inside the timed region, plus a fp32-MFMA ceiling probe after it), `value_complete_programs` and
+`cpu_baseline` (the oracle = unfused pure-torch port of the reference path, timed on the host cores over a bounded sample of the same workload;
+rank 0, N=1 only).  `--dump-outputs DIR` writes what the last timed step returned (rank 0's rows for N > 1) as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -179,6 +182,26 @@ def uni_config(irreps, soc):
     return dict(representation_nets=dict(HamGNN_pre=pre), output_nets=dict(HamGNN_out=out))
 
 
+def uni8_roofline(args, batched, t_b):
+    # roofline of the dominant kernel at THIS size: the MessagePackBlock launches of the batched chain (HIP events on the launch stream, 12 per
+    # step: two models x three layers x two blocks), SURVEY 8(d)'s reference-formulation flop count per edge and block
+    from hamgnn_amd import ops
+    ops.PROFILE_EVENTS = []
+    for _ in range(3):
+        batched()
+    torch.cuda.synchronize()
+    mp = [(s_.elapsed_time(e_) * 1e-3, rows) for (s_, e_, rows, tag) in ops.PROFILE_EVENTS if tag == "message_pack"]
+    all_ev = sum(s_.elapsed_time(e_) * 1e-3 for (s_, e_, rows, tag) in ops.PROFILE_EVENTS)
+    ops.PROFILE_EVENTS = None
+    avg_s = sum(t for t, _ in mp) / max(1, len(mp))
+    rows_l = sum(r for _, r in mp) / max(1, len(mp))
+    ach = REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * rows_l / avg_s / 1e12
+    roofline = {"kernel": "tp_is_kernel (MessagePackBlock launches of the batched chain; split launches below 300 tiles)", "bound": "mfma", "achieved": ach,
+                "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS, "traffic": None, "avg_launch_ms": avg_s * 1e3,
+                "launches_timed": len(mp), "edges_per_launch": rows_l, "fused_program_launches_share_of_step": all_ev / 3 / t_b}
+    return roofline
+
+
 def run_uni8(args, dev):
     """--workload uni8: the two-model chain of Uni-HamiltonianPredictor.py:290-319 (non-SOC universal model -> Hon_nonsoc / Hoff_nonsoc ->
     SOC / so3 model with add_H_nonsoc) over 8 mixed-Z crystals of 32-128 atoms, nao 26, set-A.  A step = all 8 crystals through both
@@ -207,13 +230,15 @@ def run_uni8(args, dev):
     singles = [(a.to(dev), b.to(dev)) for a, b in pairs]
     batch_ns, batch_soc = collate([p[0] for p in pairs]).to(dev), collate([p[1] for p in pairs]).to(dev)
 
+    last = {}
+
     def timed(fn, steps, warmup):
         for _ in range(warmup):
             fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            last["out"] = fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
 
@@ -222,39 +247,30 @@ def run_uni8(args, dev):
     ops.PROFILE_EVENTS = None
     t_pc = timed(per_crystal, args.steps, args.warmup)
     t_b = timed(batched, args.steps, args.warmup)
-    # consistency of the two issue orders (per-crystal rows == the batch's rows, crystal by crystal)
-    with torch.no_grad():
-        ob = batched()
-        oc = per_crystal()
-    hr = torch.cat([o["hamiltonian_real"] for o in oc], 0)
-    batch_vs_single = float((ob["hamiltonian_real"] - hr).abs().max() / hr.abs().max())
+    if args.dump_outputs:                                      # (the batch's rows: what the batched modes return, the same rows as the per-crystal ones)
+        dump_outputs(last["out"], args.dump_outputs)
+    batch_vs_single = None
+    if args.full:
+        # consistency of the two issue orders (per-crystal rows == the batch's rows, crystal by crystal)
+        with torch.no_grad():
+            ob = batched()
+            oc = per_crystal()
+        hr = torch.cat([o["hamiltonian_real"] for o in oc], 0)
+        batch_vs_single = float((ob["hamiltonian_real"] - hr).abs().max() / hr.abs().max())
     replays = [CapturedForward((lambda a=a, b=b: pred.predict(a, b))) for a, b in singles]
     t_gr = timed(lambda: [r() for r in replays], args.steps, args.warmup)
     lat = []
-    for r in replays:                                          # per-crystal latency of one replayed chain
-        lat.append(timed(r, max(3, args.steps), 1) * 1e3)
+    if args.full:
+        for r in replays:                                      # per-crystal latency of one replayed chain
+            lat.append(timed(r, max(3, args.steps), 1) * 1e3)
     replay_b = CapturedForward(batched)
     t_gb = timed(replay_b, args.steps, args.warmup)
     modes = {"per_crystal_eager": {"ms_per_step": t_pc * 1e3, "edges_per_s": E_total / t_pc},
-             "per_crystal_graph_replay": {"ms_per_step": t_gr * 1e3, "edges_per_s": E_total / t_gr, "latency_ms_per_crystal": lat},
+             "per_crystal_graph_replay": {"ms_per_step": t_gr * 1e3, "edges_per_s": E_total / t_gr, "latency_ms_per_crystal": lat or None},
              "batched_eager": {"ms_per_step": t_b * 1e3, "edges_per_s": E_total / t_b},
              "batched_graph_replay": {"ms_per_step": t_gb * 1e3, "edges_per_s": E_total / t_gb}}
     best = max(modes, key=lambda m: modes[m]["edges_per_s"])
-    # roofline of the dominant kernel at THIS size: the MessagePackBlock launches of the batched chain (HIP events on the launch stream, 12 per
-    # step: two models x three layers x two blocks), SURVEY 8(d)'s reference-formulation flop count per edge and block
-    ops.PROFILE_EVENTS = []
-    for _ in range(3):
-        batched()
-    torch.cuda.synchronize()
-    mp = [(s_.elapsed_time(e_) * 1e-3, rows) for (s_, e_, rows, tag) in ops.PROFILE_EVENTS if tag == "message_pack"]
-    all_ev = sum(s_.elapsed_time(e_) * 1e-3 for (s_, e_, rows, tag) in ops.PROFILE_EVENTS)
-    ops.PROFILE_EVENTS = None
-    avg_s = sum(t for t, _ in mp) / max(1, len(mp))
-    rows_l = sum(r for _, r in mp) / max(1, len(mp))
-    ach = REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * rows_l / avg_s / 1e12
-    roofline = {"kernel": "tp_is_kernel (MessagePackBlock launches of the batched chain; split launches below 300 tiles)", "bound": "mfma", "achieved": ach,
-                "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS, "traffic": None, "avg_launch_ms": avg_s * 1e3,
-                "launches_timed": len(mp), "edges_per_launch": rows_l, "fused_program_launches_share_of_step": all_ev / 3 / t_b}
+    roofline = uni8_roofline(args, batched, t_b) if args.full else None
     res = {"metric": "edges/sec (equivariant MP forward)", "value": modes[best]["edges_per_s"], "unit": "edges/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": modes[best]["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
            "dtype": "f32", "data": "synthetic",
@@ -295,6 +311,58 @@ def accuracy_vs_oracle(path):
                       f"fp32 HIP vs fp64 oracle ({time.perf_counter() - t0:.1f} s on the host)"}
 
 
+DUMP_LIMIT_BYTES = 32 * 2 ** 20
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor / number of `outputs` (a result dict, nested dicts and lists flattened to "a.b.0" names; None and strings
+    skipped) -> out_dir/<name>.npy, float64 kept, every other dtype as float32 (complex: a trailing [re, im] axis).  When the whole exceeds
+    `limit` bytes, the arrays larger than limit / 64 are cut to the same share of their rows, drawn by a fixed-seed generator per row count
+    (the same rows of every array of that length: hamiltonian_real / _imag stay aligned), kept in ascending order, their indices written
+    beside them as <name>.rows.npy (float64) -- so that two builds given the same arguments write the same sample."""
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if isinstance(v, dict) or hasattr(v, "items"):
+            for k, x in v.items():
+                walk(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for k, x in enumerate(v):
+                walk(f"{name}.{k}" if name else str(k), x)
+        elif torch.is_tensor(v):
+            t = v.detach()
+            if t.is_complex():
+                t = torch.view_as_real(t)
+            flat[name] = t if t.dtype == torch.float64 else t.float()
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            flat[name] = torch.tensor(float(v), dtype=torch.float64)
+
+    walk("", outputs)
+    row_bytes = {k: t[0].numel() * t.element_size() if t.dim() and t.shape[0] else 0 for k, t in flat.items()}
+    total = sum(t.numel() * t.element_size() for t in flat.values())
+    many = [k for k, t in flat.items() if t.dim() and t.shape[0] > 1 and t.numel() * t.element_size() > limit // 64]
+    share = 1.0
+    if total > limit:
+        fixed = total - sum(flat[k].numel() * flat[k].element_size() for k in many)
+        share = max(0.0, (limit - fixed - 256 * 2 * len(flat)) / sum(flat[k].shape[0] * (row_bytes[k] + 8) for k in many))     # (256: room for an .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    written, rows_of = {}, {}
+    for k, t in flat.items():
+        rows = None
+        if share < 1.0 and k in many:
+            n = t.shape[0]
+            if n not in rows_of:
+                gen = torch.Generator().manual_seed(20240 + n)
+                rows_of[n] = torch.randperm(n, generator=gen)[:max(1, int(n * share))].sort().values
+            rows = rows_of[n]
+            t = t.index_select(0, rows.to(t.device))
+            np.save(os.path.join(out_dir, k + ".rows.npy"), rows.double().numpy())
+        np.save(os.path.join(out_dir, k + ".npy"), t.cpu().numpy())
+        written[k] = {"shape": list(flat[k].shape), "rows_written": (None if rows is None else int(rows.numel()))}
+    return written
+
+
 class _LauncherExit(SystemExit):
     """exit of the process that only launched the ranks (not a rank's own failure)"""
 
@@ -315,6 +383,80 @@ def self_launch(n_gpus: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def roofline_of(args, model, events, E_local, dt, dev):
+    """--full: the roofline block of the dominant kernel from the per-launch HIP events of the timed region (`events`), plus the MFMA ceiling probe"""
+    from hamgnn_amd import ops
+    mp = [(s.elapsed_time(e) * 1e-3, rows, tag) for (s, e, rows, tag) in events if tag == "message_pack"]
+    all_tp = sum(s.elapsed_time(e) * 1e-3 for (s, e, rows, tag) in events)
+    n_launch = max(1, len(mp))
+    avg_s = sum(t for t, _, _ in mp) / n_launch
+    rows_per_launch = sum(r for _, r, _ in mp) / n_launch
+    # the programs of a step in launch order (ConvBlock, PairInteractionBlock per layer).  r5: the FIRST layer's programs drop the super-paths that read
+    # structurally zero input irreps (node rows out of the 0e embedding Linear, edge rows out of the 0e x Y^l pair embedding: hamgnn_conv._mark_structural_zeros),
+    # so the launches of a step are not all the same program any more: flops are summed program by program
+    # r5b: ... and the LAST PairInteractionBlock drops the output irreps the read-out head never reads (HamGNNConvE3.declare_consumer).
+    dps, full_of = [], []
+    for conv, pair in zip(model.convolutions, model.pair_interactions):
+        dps.append(conv.conv_tp._dp_for(E_local, True))        # the program the launch ran (first layer / last pair block: the reduced one)
+        full_of.append(conv.conv_tp._dp_for(E_local, False).prog)      # the complete program of the same block (every path of the reference)
+        if pair.use_skip_connections or not pair.legacy_edge_update:
+            dps.append(pair.conv_tp._dp_for(E_local, True))
+            full_of.append(pair.conv_tp._dp_for(E_local, False).prog)
+    issued_of = lambda dp: (dp.prog.mfma_per_wave - (dp.prog.mfma_odd_skipped if dp.sched is not None else 0)) * 2048.0 / 16.0
+    t_tot = sum(t for t, _, _ in mp)
+    useful_tot = sum(dps[k % len(dps)].prog.flops_per_row * r for k, (_, r, _) in enumerate(mp))
+    issued_tot = sum(issued_of(dps[k % len(dps)]) * r for k, (_, r, _) in enumerate(mp))
+    radial_tot = sum(getattr(dps[k % len(dps)].prog, "mfma_radial", 0) * 2048.0 / 16.0 * r for k, (_, r, _) in enumerate(mp))
+    split_on = os.environ.get("HG_S_SPLIT", "1") != "0" and not args.lite
+    share = [dp.prog.flops_per_row / fo.flops_per_row for dp, fo in zip(dps, full_of)]           # non-zero share of the reference formulation's flops, per launch of a step
+    ref_tot = sum(REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * r for _, r, _ in mp)
+    ref_nonzero_tot = sum(REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * share[k % len(dps)] * r for k, (_, r, _) in enumerate(mp))
+    # r6 (VERDICT r5 #4): the headline `achieved` / `frac` count, per launch, only the share of the reference formulation's flops that the launched PROGRAM still holds
+    # (a first-layer launch that drops the super-paths reading structurally zero irreps is credited with 27 % of 4.55 MFLOP per edge, not with all of it); the
+    # figure that credits every launch with the reference op graph's full flops is reported as `frac_vs_reference_op_graph`, clearly named
+    flops_tot = useful_tot if args.lite else ref_nonzero_tot
+    ach = flops_tot / t_tot / 1e12
+    kern = "is" if dps[-1].sched is not None else "seg"
+    pmc_bytes = PMC_HBM_BYTES_PER_EDGE_BLOCK[(kern, args.irreps)]
+    per_kind = {}
+    for k, (t, r, _) in enumerate(mp):
+        per_kind.setdefault(k % len(dps), []).append(t)
+    full_t = [t for k, (t, r, _) in enumerate(mp) if share[k % len(dps)] > 0.999]
+    roofline = {"kernel": ("tp_is_kernel (input-stationary" if kern == "is" else "tp_fused_kernel (segment-stationary") + " MessagePackBlock launches)", "bound": "mfma", "achieved": ach, "peak": PEAK_FP32_TFLOPS,
+                "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS, "traffic": pmc_bytes * rows_per_launch,
+                "traffic_unit": "bytes per launch (rocprofv3 PMC FETCH_SIZE x 2 + WRITE_SIZE, measured offline on the benchmarked launches of this kernel: profiles/r06_tp_is_pmc.md; "
+                                "set-B: r02b_tp_is_hbm_pmc.md, segment-stationary kernel: r01c_tp_fused_hbm_pmc.md), scaled to this launch's edge count", "avg_launch_ms": avg_s * 1e3,
+                "launches_timed": len(mp), "edges_per_launch": rows_per_launch,
+                # `achieved` / `frac`: reference-formulation flops (4.55 MFLOP per edge and block for set-A, SURVEY 8d) of the paths each launched program HOLDS.
+                # `frac_vs_reference_op_graph` credits every launch with the complete block -- incl. the flops the reference spends multiplying the structurally zero
+                # input irreps of the first layer and computing output irreps the read-out head never reads, which this build does not issue (DESIGN.md 3.5 / 3.6):
+                # a throughput-equivalent, NOT a utilisation.  `frac_full_program_launches`: the launches that run a complete program, alone.
+                "frac_vs_reference_op_graph": (ref_tot / t_tot / 1e12 / PEAK_FP32_TFLOPS if not args.lite else None),
+                "frac_full_program_launches": (REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / (sum(full_t) / max(1, len(full_t))) / 1e12 / PEAK_FP32_TFLOPS
+                                               if full_t and not args.lite else None),
+                "launch_ms_by_position_in_step": [round(1e3 * sum(v) / len(v), 3) for _, v in sorted(per_kind.items())],
+                "nonzero_flop_share_by_position": [round(x, 4) for x in share],
+                "executed_useful_tflops": useful_tot / t_tot / 1e12, "issued_mfma_tflops": issued_tot / t_tot / 1e12,
+                # r6: the radial scales (this share of the fp32-equivalent MFMAs the programs issue) run as 3 half-precision products of K = 32 on the f16 pipe; the floor of a
+                # launch that spends exactly its fp32 MFMAs at the fp32 peak and those products at the f16 peak, over the measured time -- `frac` above prices ALL flops at fp32
+                "radial_scale_share_of_issued_mfma": radial_tot / issued_tot if issued_tot else None,
+                "frac_of_mixed_pipe_floor": ((issued_tot - radial_tot) / (PEAK_FP32_TFLOPS * 1e12) + 3.0 * radial_tot / (PEAK_F16_TFLOPS * 1e12)) / t_tot * (flops_tot / issued_tot)
+                                            if (issued_tot and split_on) else None,
+                "hbm_algorithmic_GBs": REF_BYTES_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / avg_s / 1e9,
+                "hbm_frac": REF_BYTES_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / avg_s / 1e9 / PEAK_HBM_GBS,
+                "hbm_measured_GBs": pmc_bytes * rows_per_launch / avg_s / 1e9,
+                "fused_program_launches_share_of_step": all_tp / dt}
+    issued, useful = issued_tot / n_launch, useful_tot / n_launch
+    if not args.no_mfma_probe:
+        # what the fp32 matrix pipe sustains on this device right now (random operands, two waves per SIMD, nothing but MFMAs; after the
+        # timed region): the chip clocks to its power budget, so the nominal peak above is not attainable on non-trivial data.  Reported
+        # beside `peak`; `frac` stays achieved / nominal peak.
+        probe = ops.mfma_probe(dev)
+        roofline["mfma_probe_tflops"] = probe
+        roofline["issued_over_probe"] = issued / avg_s / 1e12 / probe
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -333,6 +475,10 @@ def main():
     ap.add_argument("--cpu-baseline-full", action="store_true", help="with --cpu-baseline-only: the port on the WHOLE workload with a thread sweep (minutes; meant for --workload si512 --irreps B)")
     ap.add_argument("--accuracy-from", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-accuracy", action="store_true", help="skip the accuracy leg (fp64 oracle on a bounded sub-crystal, host cores)")
+    ap.add_argument("--full", action="store_true", help="also measure / check what the headline does not need: per-launch HIP events and the roofline, the MFMA "
+                    "probe, the accuracy leg, the complete-programs pass, the CPU baseline, per-rank figures and the sharded check for N > 1 (the --no-* options above apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; a fixed, "
+                    "seeded sample of rows where the whole would exceed 32 MiB)")
     args = ap.parse_args()
     if args.cpu_baseline_only:                       # child process of the N=1 run (hard wall-clock bound in the parent)
         if args.accuracy_from:
@@ -430,8 +576,8 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    ops.PROFILE_EVENTS = []                                  # HIP event pairs around every hg_tp_fused launch (launch stream)
-    parallel.PROFILE_EVENTS = [] if world > 1 else None      # ... and around every node all-reduce
+    ops.PROFILE_EVENTS = [] if args.full else None           # --full: HIP event pairs around every hg_tp_fused launch (launch stream)
+    parallel.PROFILE_EVENTS = [] if world > 1 and args.full else None      # ... and around every node all-reduce
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]      # per-step boundaries on the launch stream (no host sync)
     t0 = time.perf_counter()
     marks[0].record()
@@ -451,6 +597,9 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    if world > 1 and args.full:
         # what every rank spent per step (HIP events on its launch stream): the edge kernel, the node all-reduces (incl. the wait for the
         # slowest rank), everything else (node-level Linears / gates, the read-out of its own edges, launch gaps)
         tp_ms = sum(s.elapsed_time(e) for (s, e, rows, tag) in events if tag == "message_pack") / args.steps
@@ -477,7 +626,7 @@ def main():
         torch.distributed.all_gather_object(per_rank, mine)
     assert torch.isfinite(out["hamiltonian"]).all()
     sharded_check = None
-    if world > 1 and not args.no_accuracy:
+    if world > 1 and args.full and not args.no_accuracy:
         # after the timed region: the SAME model on a bounded sub-crystal of the same generator, sharded over the ranks (the collective of the
         # job: RCCL on a multi-GPU node) against the unsharded forward on rank 0 -- so that a scaling record also says the sharded rows are right
         small = make_graph({"sio2_10k": "sio2_300", "si512": "si64", "mos2_1200": "mos2_48"}.get(args.workload, "sio2_300"), args.nao, soc=args.soc)
@@ -500,74 +649,7 @@ def main():
             assert sharded_check["rel_err"] < 1e-5, sharded_check
 
     # ---- roofline of the dominant kernel: the fused MessagePackBlock launches (hg_tp_is; hg_tp_fused on the fallback path)
-    mp = [(s.elapsed_time(e) * 1e-3, rows, tag) for (s, e, rows, tag) in events if tag == "message_pack"]
-    all_tp = sum(s.elapsed_time(e) * 1e-3 for (s, e, rows, tag) in events)
-    n_launch = max(1, len(mp))
-    avg_s = sum(t for t, _, _ in mp) / n_launch
-    rows_per_launch = sum(r for _, r, _ in mp) / n_launch
-    # the programs of a step in launch order (ConvBlock, PairInteractionBlock per layer).  r5: the FIRST layer's programs drop the super-paths that read
-    # structurally zero input irreps (node rows out of the 0e embedding Linear, edge rows out of the 0e x Y^l pair embedding: hamgnn_conv._mark_structural_zeros),
-    # so the launches of a step are not all the same program any more: flops are summed program by program
-    # r5b: ... and the LAST PairInteractionBlock drops the output irreps the read-out head never reads (HamGNNConvE3.declare_consumer).
-    dps, full_of = [], []
-    for conv, pair in zip(model.convolutions, model.pair_interactions):
-        dps.append(conv.conv_tp._dp_for(E_local, True))        # the program the launch ran (first layer / last pair block: the reduced one)
-        full_of.append(conv.conv_tp._dp_for(E_local, False).prog)      # the complete program of the same block (every path of the reference)
-        if pair.use_skip_connections or not pair.legacy_edge_update:
-            dps.append(pair.conv_tp._dp_for(E_local, True))
-            full_of.append(pair.conv_tp._dp_for(E_local, False).prog)
-    issued_of = lambda dp: (dp.prog.mfma_per_wave - (dp.prog.mfma_odd_skipped if dp.sched is not None else 0)) * 2048.0 / 16.0
-    t_tot = sum(t for t, _, _ in mp)
-    useful_tot = sum(dps[k % len(dps)].prog.flops_per_row * r for k, (_, r, _) in enumerate(mp))
-    issued_tot = sum(issued_of(dps[k % len(dps)]) * r for k, (_, r, _) in enumerate(mp))
-    radial_tot = sum(getattr(dps[k % len(dps)].prog, "mfma_radial", 0) * 2048.0 / 16.0 * r for k, (_, r, _) in enumerate(mp))
-    split_on = os.environ.get("HG_S_SPLIT", "1") != "0" and not args.lite
-    share = [dp.prog.flops_per_row / fo.flops_per_row for dp, fo in zip(dps, full_of)]           # non-zero share of the reference formulation's flops, per launch of a step
-    ref_tot = sum(REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * r for _, r, _ in mp)
-    ref_nonzero_tot = sum(REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * share[k % len(dps)] * r for k, (_, r, _) in enumerate(mp))
-    # r6: the headline `achieved` / `frac` count, per launch, only the share of the reference formulation's flops that the launched PROGRAM still holds
-    # (a first-layer launch that drops the super-paths reading structurally zero irreps is credited with 27 % of 4.55 MFLOP per edge, not with all of it); the
-    # figure that credits every launch with the reference op graph's full flops is reported as `frac_vs_reference_op_graph`, clearly named
-    flops_tot = useful_tot if args.lite else ref_nonzero_tot
-    ach = flops_tot / t_tot / 1e12
-    kern = "is" if dps[-1].sched is not None else "seg"
-    pmc_bytes = PMC_HBM_BYTES_PER_EDGE_BLOCK[(kern, args.irreps)]
-    per_kind = {}
-    for k, (t, r, _) in enumerate(mp):
-        per_kind.setdefault(k % len(dps), []).append(t)
-    full_t = [t for k, (t, r, _) in enumerate(mp) if share[k % len(dps)] > 0.999]
-    roofline = {"kernel": ("tp_is_kernel (input-stationary" if kern == "is" else "tp_fused_kernel (segment-stationary") + " MessagePackBlock launches)", "bound": "mfma", "achieved": ach, "peak": PEAK_FP32_TFLOPS,
-                "unit": "TFLOP/s", "frac": ach / PEAK_FP32_TFLOPS, "traffic": pmc_bytes * rows_per_launch,
-                "traffic_unit": "bytes per launch (rocprofv3 PMC FETCH_SIZE x 2 + WRITE_SIZE, measured offline on the benchmarked launches of this kernel: profiles/r06_tp_is_pmc.md; "
-                                "set-B: r02b_tp_is_hbm_pmc.md, segment-stationary kernel: r01c_tp_fused_hbm_pmc.md), scaled to this launch's edge count", "avg_launch_ms": avg_s * 1e3,
-                "launches_timed": len(mp), "edges_per_launch": rows_per_launch,
-                # `achieved` / `frac`: reference-formulation flops (4.55 MFLOP per edge and block for set-A) of the paths each launched program HOLDS.
-                # `frac_vs_reference_op_graph` credits every launch with the complete block -- incl. the flops the reference spends multiplying the structurally zero
-                # input irreps of the first layer and computing output irreps the read-out head never reads, which this build does not issue:
-                # a throughput-equivalent, NOT a utilisation.  `frac_full_program_launches`: the launches that run a complete program, alone.
-                "frac_vs_reference_op_graph": (ref_tot / t_tot / 1e12 / PEAK_FP32_TFLOPS if not args.lite else None),
-                "frac_full_program_launches": (REF_FLOPS_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / (sum(full_t) / max(1, len(full_t))) / 1e12 / PEAK_FP32_TFLOPS
-                                               if full_t and not args.lite else None),
-                "launch_ms_by_position_in_step": [round(1e3 * sum(v) / len(v), 3) for _, v in sorted(per_kind.items())],
-                "nonzero_flop_share_by_position": [round(x, 4) for x in share],
-                "executed_useful_tflops": useful_tot / t_tot / 1e12, "issued_mfma_tflops": issued_tot / t_tot / 1e12,
-                # r6: the radial scales (this share of the fp32-equivalent MFMAs the programs issue) run as 3 half-precision products of K = 32 on the f16 pipe; the floor of a
-                # launch that spends exactly its fp32 MFMAs at the fp32 peak and those products at the f16 peak, over the measured time -- `frac` above prices ALL flops at fp32
-                "radial_scale_share_of_issued_mfma": radial_tot / issued_tot if issued_tot else None,
-                "frac_of_mixed_pipe_floor": ((issued_tot - radial_tot) / (PEAK_FP32_TFLOPS * 1e12) + 3.0 * radial_tot / (PEAK_F16_TFLOPS * 1e12)) / t_tot * (flops_tot / issued_tot)
-                                            if (issued_tot and split_on) else None,
-                "hbm_algorithmic_GBs": REF_BYTES_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / avg_s / 1e9,
-                "hbm_frac": REF_BYTES_PER_EDGE_BLOCK[args.irreps] * rows_per_launch / avg_s / 1e9 / PEAK_HBM_GBS,
-                "hbm_measured_GBs": pmc_bytes * rows_per_launch / avg_s / 1e9,
-                "fused_program_launches_share_of_step": all_tp / dt}
-    issued, useful = issued_tot / n_launch, useful_tot / n_launch
-    if not args.no_mfma_probe:
-        # what the fp32 matrix pipe sustains on this device right now (random operands, two waves per SIMD, nothing but MFMAs; after the
-        # timed region): the chip clocks to its power budget, so the nominal peak above is not attainable on non-trivial data.  Reported
-        # beside `peak`; `frac` stays achieved / nominal peak.
-        probe = ops.mfma_probe(dev)
-        roofline["mfma_probe_tflops"] = probe
-        roofline["issued_over_probe"] = issued / avg_s / 1e12 / probe
+    roofline = roofline_of(args, model, events, E_local, dt, dev) if args.full else None
 
     res = {"metric": "edges/sec (equivariant MP forward)", "value": E_total * args.steps / dt, "unit": "edges/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_median": median_ms,
@@ -579,7 +661,7 @@ def main():
            "roofline": roofline, "compile_s": compile_s,
            # arithmetic of the hot kernel (r6): everything in fp32 MFMAs EXCEPT the radial scale S = W3^T h (27.5 % of a block's fp32-equivalent MFMAs), which runs on the
            # half-precision matrix pipe with both operands split into two f16 terms (22 significant bits, fp32 accumulation): 6 x 16 pipe cycles per row tile instead of 16 x 32.
-           # `roofline` counts its flops as the fp32 flops they replace and prices them against the fp32 peak.  Accuracy against the fp64 oracle: the `accuracy` field of this line
+           # `roofline` counts its flops as the fp32 flops they replace and prices them against the fp32 peak.  Accuracy against the fp64 oracle: the `accuracy` field of a --full line
            # (2.28e-6 with, 2.24e-6 without); HG_S_SPLIT=0 = the all-fp32 form (229.5 ms per step on sio2_10k against 202.9: profiles/r06_tp_is.md)
            "radial_scale_arithmetic": ("fp32 MFMAs (HG_S_SPLIT=0)" if os.environ.get("HG_S_SPLIT", "1") == "0" or args.lite
                                        else "v_mfma_f32_16x16x32_f16 on split operands (hi + 2^-11 lo, 22 bits), fp32 accumulation"),
@@ -595,7 +677,7 @@ def main():
         res["ranks_seen"] = {"backend": "RCCL (torch.distributed 'nccl')" if backend == "nccl" else backend, "world_size": torch.distributed.get_world_size(),
                              "distinct_devices": len({(h, d) for h, d, _ in idents}), "max_over_mean_edges": max(r["edges"] for r in per_rank) * world / E_total}
     if rank == 0:
-        if world == 1 and not args.no_accuracy:
+        if world == 1 and args.full and not args.no_accuracy:
             # accuracy of THIS model (same weights) on a bounded sub-crystal of the same generator: the HIP forward here, the fp64 oracle in a
             # child process on the host cores -- reported next to the throughput, never inside the timed region
             import subprocess
@@ -617,7 +699,7 @@ def main():
                     res["accuracy"] = json.loads(line[len("ACCURACY "):])
             except Exception as exc:
                 res["accuracy"] = {"rel_max": None, "mae": None, "sample": f"failed: {exc!r}"[:200]}
-        if world == 1 and not args.lite and not args.no_complete_pass:
+        if world == 1 and args.full and not args.lite and not args.no_complete_pass:
             # the like-for-like figure against the reference's op graph: the SAME model with every path of every block issued (HG_STRUCT_ZEROS=0 HG_DEAD_OUT=0:
             # no structural-zero shortcut, no unread-irreps shortcut), recompiled and timed AFTER the timed region -- `value` is never this pass
             prev_env = {k: os.environ.get(k) for k in ("HG_STRUCT_ZEROS", "HG_DEAD_OUT")}
@@ -643,7 +725,7 @@ def main():
                         os.environ.pop(k, None)
                     else:
                         os.environ[k] = v
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             import subprocess
             try:
                 cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--workload", args.workload,

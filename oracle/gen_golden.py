@@ -237,8 +237,36 @@ def _save(name, **groups):
         for k, v in _np(d).items():
             flat[f"{gname}/{k}"] = v
     os.makedirs(GOLD, exist_ok=True)
-    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **flat)
-    print(f"  wrote tests/golden/{name}.npz  ({os.path.getsize(os.path.join(GOLD, name + '.npz')) / 1024:.0f} KiB)")
+    for path in write_parts(os.path.join(GOLD, name), flat):
+        print(f"  wrote tests/golden/{os.path.basename(path)}  ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
+GOLD_PART_BYTES = 960 * 1024
+
+
+def write_parts(stem, flat, limit=GOLD_PART_BYTES):
+    """{key: array} -> <stem>.npz (+ <stem>.part1.npz, .part2.npz ... when one compressed file would exceed `limit` bytes: no committed file is
+    larger than 1 MiB), keys in sorted order, each file as full as it can be; tests/gpu_checks.load reads the parts back as one fixture."""
+    import io
+    parts, cur = [], {}
+    for k in sorted(flat):
+        trial = dict(cur, **{k: flat[k]})
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **trial)
+        if cur and buf.tell() > limit:
+            parts.append(cur)
+            cur = {k: flat[k]}
+        else:
+            cur = trial
+    parts.append(cur)
+    stale = 1
+    while os.path.exists(f"{stem}.part{stale}.npz"):
+        os.remove(f"{stem}.part{stale}.npz")
+        stale += 1
+    paths = [stem + ".npz"] + [f"{stem}.part{i}.npz" for i in range(1, len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
 
 
 def _check(a, b, what, tol=1e-10):

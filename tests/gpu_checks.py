@@ -20,11 +20,18 @@ SAME_MATH_TOL = TOL / 2
 
 
 def load(name):
-    z = np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False)
+    """a fixture: <name>.npz and, for one that would not fit a 1 MiB file, its <name>.part1.npz, .part2.npz ... (oracle/gen_golden.write_parts)"""
+    paths, k = [os.path.join(GOLD, name + ".npz")], 1
+    while os.path.exists(os.path.join(GOLD, f"{name}.part{k}.npz")):
+        paths.append(os.path.join(GOLD, f"{name}.part{k}.npz"))
+        k += 1
     out = {}
-    for k in z.files:
-        g, kk = k.split("/", 1)
-        out.setdefault(g, {})[kk] = z[k]
+    for path in paths:
+        z = np.load(path, allow_pickle=False)
+        for k in z.files:
+            g, kk = k.split("/", 1)
+            assert kk not in out.get(g, {}), (path, k)
+            out.setdefault(g, {})[kk] = z[k]
     return out
 
 

@@ -27,3 +27,33 @@ def test_launcher_and_gpus_flag_must_agree():
     env = dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0")
     cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], capture_output=True, text=True, timeout=300, env=env)
     assert cp.returncode != 0 and "WORLD_SIZE" in cp.stderr
+
+
+def test_output_dump_is_bounded_and_the_same_sample_every_time(tmp_path):
+    """bench.py --dump-outputs: arrays as float32 (float64 kept), numbers as 0-d float64, None skipped; above the size limit the large arrays are cut to
+    the same seeded sample of rows for every array of that length (indices beside them), small ones stay whole, and a second call on the same
+    outputs writes the same files"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {"hamiltonian_real": torch.randn(4000, 36, generator=g), "hamiltonian_imag": torch.randn(4000, 36, generator=g),
+            "energies": torch.randn(7, dtype=torch.float64, generator=g), "sparsity_ratio": 0.5, "band_energy": None, "parts": [torch.arange(3)]}
+    limit = 200_000
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert files == ["energies.npy", "hamiltonian_imag.npy", "hamiltonian_imag.rows.npy", "hamiltonian_real.npy", "hamiltonian_real.rows.npy", "parts.0.npy",
+                     "sparsity_ratio.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    rows = np.load(tmp_path / "a" / "hamiltonian_real.rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 4000 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "a" / "hamiltonian_imag.rows.npy"))
+    re = np.load(tmp_path / "a" / "hamiltonian_real.npy")
+    assert re.dtype == np.float32 and re.shape == (len(rows), 36)
+    np.testing.assert_array_equal(re, outs["hamiltonian_real"].numpy()[rows.astype(np.int64)])
+    assert np.load(tmp_path / "a" / "energies.npy").dtype == np.float64 and np.load(tmp_path / "a" / "parts.0.npy").dtype == np.float32
+    assert float(np.load(tmp_path / "a" / "sparsity_ratio.npy")) == 0.5

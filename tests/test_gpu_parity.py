@@ -507,7 +507,7 @@ def test_bench_script_two_rank_path_on_one_gpu(launcher):
     env = dict(os.environ, HG_BENCH_SAME_DEVICE="1", HG_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "si512", "--irreps", "B"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "si512", "--irreps", "B", "--full"]
     head = [sys.executable] if launcher == "bare" else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                                          "--master-port", "29547"]
     cp = subprocess.run(head + tail, capture_output=True, text=True, timeout=600, env=env)
@@ -531,6 +531,34 @@ def test_bench_script_propagates_a_failing_rank():
     cp = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "si64", "--irreps", "B"],
                         capture_output=True, text=True, timeout=300, env=env)
     assert cp.returncode != 0 and "BENCH_RANK_FAILURE" in cp.stderr and not [l for l in cp.stdout.splitlines() if l.startswith("{")], cp.stdout[-800:] + cp.stderr[-800:]
+
+
+def test_bench_script_plain_run_dumps_its_last_step(tmp_path):
+    """a plain `bench.py` line (no --full): the headline fields, none of the legs that take runs of their own; `--dump-outputs DIR` writes the
+    Hamiltonian rows of the last timed step, and a second process with the same arguments writes the same arrays (eager forwards are bit-reproducible)"""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dirs = [], []
+    for k in range(2):
+        d = str(tmp_path / f"run{k}")
+        cp = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "si2", "--dump-outputs", d],
+                            capture_output=True, text=True, timeout=300)
+        assert cp.returncode == 0, cp.stdout[-1500:] + cp.stderr[-1500:]
+        out = [l for l in cp.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, cp.stdout[-1500:]
+        lines.append(json.loads(out[0]))
+        dirs.append(d)
+    r = lines[0]
+    print({k: r[k] for k in ("value", "ms_per_step", "steps")})
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "edges/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["roofline"] is None and not {"accuracy", "cpu_baseline", "value_complete_programs"} & set(r)
+    H = np.load(os.path.join(dirs[0], "hamiltonian.npy"))
+    n_rows = int(r["config"]["workload"].split(" atoms")[0].split()[-1]) + int(r["config"]["workload"].split(" directed edges")[0].split()[-1])
+    assert H.dtype == np.float32 and H.shape == (n_rows, 19 * 19) and np.isfinite(H).all() and np.abs(H).max() > 0
+    assert sorted(os.listdir(dirs[0])) == sorted(os.listdir(dirs[1]))
+    for f in os.listdir(dirs[0]):
+        np.testing.assert_array_equal(np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f)), err_msg=f)
 
 
 def test_radial_mlp_with_five_hidden_layers_vs_oracle():

@@ -7,16 +7,16 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag
 mkdir -p $out
-python bench.py --steps 20 --warmup 5 > $out/bench_sio2_10k_setA.json 2> $out/bench_sio2.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_sio2_10k_setA.json 2> $out/bench_sio2.err
 if [ "${2:-}" = "full" ]; then
-python bench.py --steps 20 --warmup 5 --workload si512 --irreps B --no-accuracy > $out/bench_si512_setB.json 2>> $out/bench_sio2.err
-python bench.py --steps 20 --warmup 5 --workload mos2_1200 --no-cpu-baseline --no-accuracy > $out/bench_mos2_1200_setA.json 2>> $out/bench_sio2.err
-python bench.py --steps 20 --warmup 5 --workload mos2_1200 --soc --no-cpu-baseline --no-accuracy > $out/bench_mos2_1200_setA_soc.json 2>> $out/bench_sio2.err
-python bench.py --steps 50 --warmup 5 --workload si2 --no-cpu-baseline --no-accuracy > $out/bench_si2_setA.json 2>> $out/bench_sio2.err
-python bench.py --workload uni8 --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy > $out/bench_uni8_setA.json 2>> $out/bench_sio2.err
-python bench.py --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sio2_10k_setA_lite.json 2>> $out/bench_sio2.err
+python bench.py --full --steps 20 --warmup 5 --workload si512 --irreps B --no-accuracy > $out/bench_si512_setB.json 2>> $out/bench_sio2.err
+python bench.py --full --steps 20 --warmup 5 --workload mos2_1200 --no-cpu-baseline --no-accuracy > $out/bench_mos2_1200_setA.json 2>> $out/bench_sio2.err
+python bench.py --full --steps 20 --warmup 5 --workload mos2_1200 --soc --no-cpu-baseline --no-accuracy > $out/bench_mos2_1200_setA_soc.json 2>> $out/bench_sio2.err
+python bench.py --full --steps 50 --warmup 5 --workload si2 --no-cpu-baseline --no-accuracy > $out/bench_si2_setA.json 2>> $out/bench_sio2.err
+python bench.py --full --workload uni8 --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy > $out/bench_uni8_setA.json 2>> $out/bench_sio2.err
+python bench.py --full --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_sio2_10k_setA_lite.json 2>> $out/bench_sio2.err
 fi
-rocprofv3 --kernel-trace --stats -d $out/prof --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-accuracy > $out/bench_profiled.json 2> $out/prof.err
+rocprofv3 --kernel-trace --stats -d $out/prof --output-format csv -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-accuracy > $out/bench_profiled.json 2> $out/prof.err
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/sio2_10k_kernel_stats.csv
 f=$(find $out/prof -name "*kernel_trace.csv" | head -1)
 head -1 $f > $out/sio2_10k_kernel_trace_tp_is.csv; grep "tp_is_kernel" $f >> $out/sio2_10k_kernel_trace_tp_is.csv

@@ -14,4 +14,4 @@ for l in sys.stdin:
     d[r['tag']].append((r['ms'], r['checksum']))
 for k, v in d.items(): print(k, ' '.join(f'{m:.3f}' for m, _ in v), 'checksum', v[0][1])
 "
-if [ "${2:-}" = bench ]; then python bench.py --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_lite.json 2> $out/bench.err; cut -c1-300 $out/bench_lite.json; fi
+if [ "${2:-}" = bench ]; then python bench.py --full --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_lite.json 2> $out/bench.err; cut -c1-300 $out/bench_lite.json; fi

@@ -16,4 +16,4 @@ for l in sys.stdin:
     d[r['tag']].append(r['ms'])
 for k, v in d.items(): print(k, ' '.join(f'{m:.3f}' for m in v))
 "
-if [ "${2:-}" = bench ]; then python bench.py --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_lite.json 2> $out/bench.err; cut -c1-300 $out/bench_lite.json; tail -3 $out/bench.err; fi
+if [ "${2:-}" = bench ]; then python bench.py --full --lite --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_lite.json 2> $out/bench.err; cut -c1-300 $out/bench_lite.json; tail -3 $out/bench.err; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-call A/B of the two exact shortcuts on the benchmark crystal: complete programs / structural zeros only / both (the default)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; out=gpurun_out/${1:-r05ab}; mkdir -p $out
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-accuracy --no-mfma-probe"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-accuracy --no-mfma-probe"
 HG_STRUCT_ZEROS=0 HG_DEAD_OUT=0 $B > $out/bench_complete_programs.json 2>/dev/null
 HG_DEAD_OUT=0 $B > $out/bench_zeros_only.json 2>/dev/null
 $B > $out/bench_default.json 2>/dev/null

@@ -7,7 +7,7 @@ for rep in 1 2; do
   for n in base:4 nw8:8; do
     name=${n%%:*}; w=${n##*:}
     for wl in si2 si64; do
-      HG_IS_WAVES=$w HG_LIB_PATH=$V/lib_$name.so timeout 200 python bench.py --steps 50 --warmup 5 --workload $wl --no-cpu-baseline --no-accuracy --no-mfma-probe 2>/dev/null | python -c "
+      HG_IS_WAVES=$w HG_LIB_PATH=$V/lib_$name.so timeout 200 python bench.py --full --steps 50 --warmup 5 --workload $wl --no-cpu-baseline --no-accuracy --no-mfma-probe 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', '$wl', round(r['ms_per_step'],3), round(r.get('ms_per_step_median',0),3), r['roofline']['launch_ms_by_position_in_step'])" >> $out/ab.log
     done
