@@ -193,9 +193,12 @@ def _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef
     return {"irreps": irr, "sh": sh, "kernel": kern, "rel_err": 0.0 if scale < 1e-12 else rel(y, out)}
 
 
-def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedule="auto", E=83, radial=(16, 16)):
+def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedule="auto", E=83, radial=(16, 16), parts=None, gather=False):
     """SURVEY 8f-3 (first step): data gradient of one MessagePackBlock forward on the GPU (adjoint program on the same HIP kernels) vs
-    torch.autograd through the fp64 oracle.  Random irreps set unless given."""
+    torch.autograd through the fp64 oracle.  Random irreps set unless given.
+    parts: workgroups per 16-edge tile forced for the adjoint launch (HG_IS_PARTS; 1 = the large-graph launch `tp_is_kernel<false, false>`).
+    gather: the output gradient is drawn as NODE rows [7, D] and handed over with `gather=receivers`, as the backbone hands the gradient of
+    a ConvBlock's aggregate (gathered and rotated inside the kernel's staging); the oracle's loss reads the gathered rows."""
     from oracle import hamgnn_ref as R, e3
     from hamgnn_amd import nn as hnn, ops, plan as P
     from tests.test_plan_emu import _random_irreps
@@ -219,39 +222,57 @@ def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedu
         n = torch.nn.functional.normalize(vec, dim=-1)
         shv = e3.spherical_harmonics(list(range(lsh + 1)), n, True, "component")
         rbf = torch.randn(E, 8, generator=g)
-        G = torch.randn(E, ref.irreps_node_feats.dim, generator=g)
-        (ref(src, dst, ef, shv, rbf) * G).sum().backward()
+        N_ = 7
+        G = torch.randn(N_ if gather else E, ref.irreps_node_feats.dim, generator=g)
+        recv = torch.randint(0, N_, (E,), generator=g) if gather else None
+        (ref(src, dst, ef, shv, rbf) * (G[recv] if gather else G)).sum().backward()
     finally:
         torch.set_default_dtype(prev)
     m = load_weights(hnn.MessagePackBlock(irr, irr, sh, irr, 8, list(radial)), {k: v.detach().numpy() for k, v in ref.state_dict().items()})
     os.environ["HG_MP_KERNEL"] = schedule
     try:
         m.compile(device, unrotate=True)
-        m.compile_adjoint(device)
     finally:
         os.environ.pop("HG_MP_KERNEL", None)
     lay = P.PlanarLayout(irr)
     lm = max(lmax, lsh)
     v = torch.stack([n[:, 2], n[:, 0], n[:, 1]], 1) * 2.0          # e3nn axis order (y, z, x) -> physical (x, y, z)
     jtab = torch.from_numpy(P.wigner_jtab(lm)).to(device)
-    ei = torch.stack([torch.zeros(E, dtype=torch.long), torch.ones(E, dtype=torch.long)]).to(device)
-    geo = ops.Geometry(torch.zeros(2, 3, device=device), ei, v.float().to(device), 8.0, 8, lm, jtab)
+    if gather:                                                 # (the edge vectors are given: the nodes only name the rows the kernel gathers)
+        ei = torch.stack([torch.zeros(E, dtype=torch.long), recv]).to(device)
+    else:
+        ei = torch.stack([torch.zeros(E, dtype=torch.long), torch.ones(E, dtype=torch.long)]).to(device)
+    geo = ops.Geometry(torch.zeros(N_ if gather else 2, 3, device=device), ei, v.float().to(device), 8.0, 8, lm, jtab)
     geo.rbf = rbf.float().to(device).contiguous()
     imap = torch.from_numpy(lay.index_map().astype(np.int32)).to(device)
     rot = torch.from_numpy(P.rotate_table(lay)).to(device)
-    gs, gd, gf = m.backward_data(ops.to_planar(G.float().to(device), imap, lay.dim), geo, out_is_global=True)
+    os.environ["HG_MP_KERNEL"] = schedule
+    if parts is not None:                                      # workgroups per 16-edge tile of the adjoint launch (1: the large-graph path)
+        os.environ["HG_IS_PARTS"] = str(parts)
+    try:
+        m.compile_adjoint(device)
+        gs, gd, gf = m.backward_data(ops.to_planar(G.float().to(device), imap, lay.dim), geo, out_is_global=True, gather=geo.dst if gather else None)
+        dpa = m._dp_adj
+        parts_used = dpa.is_parts_for(E) if dpa.sched is not None else 0       # what the launch above asked the schedule for (an int, or "lds")
+    finally:
+        os.environ.pop("HG_MP_KERNEL", None)
+        os.environ.pop("HG_IS_PARTS", None)
     gf = ops.rotate_gather(gf, None, geo, rot, transpose=True)                      # edge frame -> global frame
     torch.cuda.synchronize()
     scale = max(float(t.grad.abs().max()) for t in (src, dst, ef))
     err = lambda a, t: 0.0 if scale < 1e-12 else float((ops.from_planar(a, imap).double().cpu() - t.grad).abs().max()) / scale
-    return {"irreps": irr, "sh": sh, "kernel": "is" if m._dp_adj.sched is not None else "seg",
-            "parts": int(m._dp_adj.sched.part_table.shape[0]) if m._dp_adj.sched is not None else 0,
+    return {"irreps": irr, "sh": sh, "kernel": "is" if dpa.sched is not None else "seg",
+            "parts": int(dpa.sched.part_table.shape[0]) if dpa.sched is not None else 0,
+            "parts_used": parts_used, "fixed_parts": dpa.fixed_parts, "E": E, "gather": bool(gather),
             "g_src_rel_err": err(gs, src), "g_dst_rel_err": err(gd, dst), "g_edge_rel_err": err(gf, ef)}
 
 
-def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=53, radial=(16, 16), num_radial=8):
+def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=53, radial=(16, 16), num_radial=8, fp32_ref=False):
     """gradients of EVERY parameter of a MessagePackBlock (TP weights, linear_scaler, linear_out, all radial MLP layers, both
-    branches) on the GPU (materialisation programs on the fused kernels + GEMMs over the edges) vs torch.autograd through the fp64 oracle"""
+    branches) on the GPU (materialisation programs on the fused kernels + GEMMs over the edges) vs torch.autograd through the fp64 oracle.
+    `fused_route` of the result: the block took csrc/tp_wgrad.hip (64-wide last radial layer) and not the materialisation programs.
+    fp32_ref: also evaluate the SAME oracle module cast to float32 with CPU autograd and report its error against the fp64 gradients under the same
+    metric (`fp32_ref_rel_err`): what a plain fp32 evaluation of these sums over E edges achieves -- the yardstick of a bar for a large E."""
     from oracle import hamgnn_ref as R, e3
     from hamgnn_amd import nn as hnn, ops, plan as P
     from tests.test_plan_emu import _random_irreps
@@ -283,6 +304,19 @@ def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=
         want = {k: p.grad.clone() for k, p in ref.named_parameters()}
     finally:
         torch.set_default_dtype(prev)
+    metric = lambda a, w: float((a.double().cpu().reshape(w.shape) - w).abs().max()) / max(float(w.abs().max()), 1e-3)
+    ref32_err = None
+    if fp32_ref:
+        import copy
+        r32 = copy.deepcopy(ref).float()
+        for p_ in r32.parameters():
+            p_.grad = None
+        f32 = lambda t: t.detach().float()
+        y32 = r32(f32(x)[s_], f32(x)[r_], f32(ef), f32(shv), f32(rbf))
+        assert y32.dtype == torch.float32
+        (y32 * f32(G)).sum().backward()
+        e32 = {k: metric(p_.grad, want[k]) for k, p_ in r32.named_parameters()}
+        ref32_err = max(e32.values())
     m = load_weights(hnn.MessagePackBlock(irr, irr, sh, irr, num_radial, list(radial)), {k: v.detach().numpy() for k, v in ref.state_dict().items()})
     m.compile(device, unrotate=True)
     lay = P.PlanarLayout(irr)
@@ -300,14 +334,23 @@ def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=
     got = m.backward_weights(pl(x), pl(x), f_rot, geo, rot, pl(G), out_is_global=True, chunk=32)
     torch.cuda.synchronize()
     assert set(got) == set(want), sorted(set(got) ^ set(want))[:4]
-    errs = {k: float((got[k].double().cpu().reshape(want[k].shape) - want[k]).abs().max()) / max(float(want[k].abs().max()), 1e-3) for k in want}
-    return {"irreps": irr, "sh": sh, "max_rel_err": max(errs.values()), "worst": max(errs, key=errs.get)}
+    errs = {k: metric(got[k], want[k]) for k in want}
+    wgs = getattr(m, "_wgrad", None)
+    dwf = m._wgrad_fused_for(wgs[0], got[next(iter(got))].device) if wgs else None          # (cached by backward_weights: the tables that call ran, or None)
+    res = {"irreps": irr, "sh": sh, "E": E, "max_rel_err": max(errs.values()), "worst": max(errs, key=errs.get), "fused_route": dwf is not None,
+           "nsplit": dwf.nsplit_for(E) if dwf is not None else 0}
+    if fp32_ref:
+        res["fp32_ref_rel_err"] = ref32_err
+    return res
 
 
-def check_full_backward(device="cuda", n_atoms=6, seed=4, legacy=False, num_layers=2, nao=19, metric="mse", irr=None, sh=None, radial=(16, 16), num_radial=8, crystals=1, soc=None, charge=False, corr=False, transformer=False, lite=False, zps=False, sparsity=False, split_losses=False, bands=False, num_types=20):
+def check_full_backward(device="cuda", n_atoms=6, seed=4, legacy=False, num_layers=2, nao=19, metric="mse", irr=None, sh=None, radial=(16, 16), num_radial=8, crystals=1, soc=None, charge=False, corr=False, transformer=False, lite=False, zps=False, sparsity=False, split_losses=False, bands=False, num_types=20, parts=None, spy=False):
     """the whole model (HamGNNConvE3 + non-SOC HamGNNPlusPlusOut), loss(hamiltonian, target) -> gradient of EVERY
     parameter by hamgnn_amd.training.training_step (all block-level backwards chained on the HIP kernels) vs torch.autograd through the
-    fp64 oracle with the same weights"""
+    fp64 oracle with the same weights.
+    parts: workgroups per 16-edge tile forced for every input-stationary launch of the step (HG_IS_PARTS; 1 = the large-graph launches).
+    spy: the step's ops.tp_fused / ops.tp_wgrad calls are recorded (result["launches"]: tag, rows, workgroups per tile asked for, fused node scatter given,
+    splits of the weight-gradient kernel) -- which launch shapes the comparison actually covered."""
     from oracle import hamgnn_ref as R
     from hamgnn_amd.data import synthetic as S
     from hamgnn_amd.models.hamgnn_conv import HamGNNConvE3
@@ -419,15 +462,40 @@ def check_full_backward(device="cuda", n_atoms=6, seed=4, legacy=False, num_laye
                                                  **(skw if soc else dict(soc_switch=False))),
                                dict(rh.state_dict()))).to(device)
     gd = g.to(device)
-    if split_losses:
-        half = target.shape[0] // 2
-        gd["hamiltonian_real"], gd["hamiltonian_imag"] = target[:half].float().to(device), target[half:].float().to(device)
-        gd["hamiltonian"] = target.float().to(device)
-        r = training_step(model, gd, losses=losses)
-    elif bands:
-        r = training_step(model, gd, losses=losses)
-    else:
-        r = training_step(model, gd, metric=metric, target=target.float().to(device))
+    from hamgnn_amd import ops
+    launches = []
+    real_fused, real_wgrad = ops.tp_fused, ops.tp_wgrad
+
+    def spy_fused(dp, srcs, rows, *a, **kw):
+        is_ = dp.sched is not None
+        launches.append(dict(op="tp_fused", tag=kw.get("tag", "linear"), rows=int(rows), kernel="is" if is_ else "seg", parts=dp.is_parts_for(int(rows)) if is_ else 0,
+                             fixed_parts=dp.fixed_parts, reduce=kw.get("reduce") is not None))
+        return real_fused(dp, srcs, rows, *a, **kw)
+
+    def spy_wgrad(dwf, srcs, g_, *a, **kw):
+        rows = int(g_.shape[0])
+        launches.append(dict(op="tp_wgrad", tag="tp_wgrad", rows=rows, nsplit=int(kw.get("nsplit") or dwf.nsplit_for(rows))))
+        return real_wgrad(dwf, srcs, g_, *a, **kw)
+
+    if parts is not None:
+        os.environ["HG_IS_PARTS"] = str(parts)
+    if spy:
+        ops.tp_fused, ops.tp_wgrad = spy_fused, spy_wgrad
+    try:
+        if split_losses:
+            half = target.shape[0] // 2
+            gd["hamiltonian_real"], gd["hamiltonian_imag"] = target[:half].float().to(device), target[half:].float().to(device)
+            gd["hamiltonian"] = target.float().to(device)
+            r = training_step(model, gd, losses=losses)
+        elif bands:
+            r = training_step(model, gd, losses=losses)
+        else:
+            r = training_step(model, gd, metric=metric, target=target.float().to(device))
+    finally:
+        if spy:
+            ops.tp_fused, ops.tp_wgrad = real_fused, real_wgrad
+        if parts is not None:
+            os.environ.pop("HG_IS_PARTS", None)
     if device != "cpu":
         torch.cuda.synchronize()
     if sparsity:                                               # Model.py:158-162: hamiltonian-type losses x predictions['sparsity_ratio'] (the head's
@@ -443,6 +511,8 @@ def check_full_backward(device="cuda", n_atoms=6, seed=4, legacy=False, num_laye
             worst[k] = float((p.grad.double().cpu().reshape(want.shape) - want).abs().max()) / max(float(want.abs().max()), 1e-6)
     k = max(worst, key=worst.get)
     out.update(n_params=len(worst), max_rel_err=worst[k], worst=k, top=sorted(worst.items(), key=lambda kv: -kv[1])[:5])
+    if spy:
+        out["launches"] = launches
     return out
 
 
@@ -2228,6 +2298,28 @@ def check_tp_wgrad_kernel(device="cuda", seed=0, irr=None, sh=None, E=150, nspli
     res = {"acc_rel_err": float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)),
            "gs_rel_err": max(float(np.abs(x.double().cpu().numpy() - y).max() / max(np.abs(y).max(), 1e-30)) for x, y in zip(gs, gs_ref)),
            "units": int(wf.units.shape[0]), "irreps": irr, "sh": sh}
+    # the splits one by one: every block is a sub-sum of the same fp32 products (same bar, against the largest entry of the summed blocks)
+    a_s, b_s = acc.double().cpu().numpy()[:, used], acc_ref[:, used]
+    res["acc_split_rel_err"] = float(np.abs(a_s - b_s).max() / max(np.abs(b).max(), 1e-30))
+    # splits beyond a unit's iterations (csrc/tp_wgrad.hip:wg_range: it0 >= it1) run no edge tile: the accumulator blocks of their busy waves come back as the
+    # zeros the registers were initialised with -- exactly, whatever the LDS held
+    T, acc_h = -(-E // 16), acc.cpu().numpy()
+    empty_blocks, empty_max, ets = 0, 0.0, set()
+    for U in wf.units.astype(np.int64):
+        nsrc, ET, G1 = int(U[0]), int(U[8]), int(U[12])
+        NI = -(-T // ET)
+        per = -(-NI // nsplit)
+        ets.add(ET)
+        for w in range(4):
+            busy, _, _, _, _, _, g_mulp, _, accoff, _ = U[P.WG_WREC + P.WG_WREC_I32 * w:P.WG_WREC + P.WG_WREC_I32 * (w + 1)]
+            if not busy:
+                continue
+            n = (nsrc * G1 + -(-int(g_mulp) // 16)) * 256
+            for split in range(nsplit):
+                if split * per >= NI:
+                    empty_blocks += 1
+                    empty_max = max(empty_max, float(np.abs(acc_h[split, accoff:accoff + n]).max()))
+    res.update(E=E, nsplit=nsplit, edge_tiles_per_iteration=sorted(ets), empty_split_blocks=empty_blocks, empty_split_max_abs=empty_max)
     return res
 
 

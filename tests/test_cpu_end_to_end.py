@@ -63,6 +63,26 @@ def test_soc_head_backward_vs_autograd(cpu_backend, kw):
     assert all(v < G.TOL for k, v in r.items() if k.endswith("rel_err")), r
 
 
+def test_large_graph_backward_checks_run_on_the_stand_ins(cpu_backend):
+    """the options of the GPU checks behind tests/test_gpu_backward_large_path.py through the host code on the CPU stand-ins: the launches they mean to test ARE the
+    single-part / gathered / fused-scatter / fused-weight-gradient ones (pinned here: the checks' plumbing and the dispatch decisions, and the host glue of the
+    fused node scatter under a tape)"""
+    r = G.check_message_pack_backward(device="cpu", seed=0, parts=1, E=17, gather=True)
+    assert r["kernel"] == "is" and r["parts_used"] == 1 and r["parts"] == 1 and r["gather"], r
+    assert max(r["g_src_rel_err"], r["g_dst_rel_err"], r["g_edge_rel_err"]) < G.TOL, r
+    assert G.check_message_pack_backward(device="cpu", seed=0, E=17)["parts_used"] > 1          # (unforced, 17 edges are a split launch)
+    r = G.check_message_pack_weight_grads(device="cpu", seed=3, radial=(16, 64), E=21, fp32_ref=True)
+    assert r["fused_route"] and r["max_rel_err"] < G.TOL and 0.0 < r["fp32_ref_rel_err"] < G.TOL, r
+    assert not G.check_message_pack_weight_grads(device="cpu", seed=3, E=21)["fused_route"]
+    r = G.check_full_backward(device="cpu", radial=(16, 64), num_types=24, n_atoms=2, seed=5, parts=1, spy=True)
+    mp = [l for l in r["launches"] if l["tag"] in ("message_pack", "message_pack_adjoint")]
+    assert mp and all(l["kernel"] == "is" and l["parts"] == 1 for l in mp) and any(l["reduce"] for l in mp), r["launches"]
+    assert any(l["op"] == "tp_wgrad" for l in r["launches"]), r["launches"]
+    assert r["loss_rel_err"] < G.TOL and r["max_rel_err"] < G.TOL, r
+    from hamgnn_amd import ops
+    assert ops.tp_fused.__name__ != "spy_fused" and "HG_IS_PARTS" not in __import__("os").environ      # the spy and the forced parts are undone
+
+
 def test_small_graph_reproducibility_check_runs_on_the_stand_ins(cpu_backend):
     """the r6 GPU check (split launches bit-reproducible) through the host code on the CPU stand-ins: the launches it means to test ARE split launches
     (the stand-ins are deterministic by construction: what is pinned here is the check's plumbing and the dispatch decision)"""

@@ -915,6 +915,25 @@ def test_message_pack_weight_gradients_fused_vs_autograd(seed):
         assert float((got[k].reshape(want[k].shape) - want[k]).abs().max()) < 2e-6 * max(scale, 1e-3), (k, irr, sh)
 
 
+@pytest.mark.parametrize("E", [4095, 4096, 4097, 4111, 65539])
+def test_ht_times_batched_partial_products(E):
+    """backward_mp._ht_times (h^T gs of the last radial layer's weight gradient): from 4096 edges on it is 16 batched partial products over E // 16 rows each + a
+    ragged tail + a fixed-order sum.  Against the fp64 product; a different but equally valid order of the same fp32 sum may cost twice the plain fp32 GEMM's
+    error on the same data (floor 1e-6).  4095: the plain branch; 4096: no tail; 4097 / 4111: 1- and 15-row tails; 65539: 3-row tail, 4096-row batches.
+    Measured (max |diff| / max |want|, batched vs plain h.t() @ gs): 4095 5.2e-7 / 5.2e-7, 4096 3.4e-7 / 3.7e-7, 4097 3.2e-7 / 3.7e-7, 4111 2.2e-7 / 3.0e-7,
+    65539 4.2e-7 / 3.8e-7."""
+    import torch
+    from hamgnn_amd.backward_mp import _ht_times
+    gen = torch.Generator().manual_seed(E)
+    h, gs = torch.randn(E, 64, generator=gen), torch.randn(E, 40, generator=gen)
+    want = h.double().t() @ gs.double()
+    err = lambda a: float((a.double() - want).abs().max() / want.abs().max())
+    got, plain = err(_ht_times(h, gs)), err(h.t() @ gs)
+    print({"E": E, "batched_rel_err": got, "plain_fp32_rel_err": plain})
+    assert _ht_times(h, gs).shape == (64, 40)
+    assert got < max(2 * plain, 1e-6), (E, got, plain)      # (one dropped tail row of 4097 would be a 1e-2 relative error)
+
+
 @pytest.mark.parametrize("seed", [(0, False), (1, False), (0, True), (1, True)], ids=["0", "1", "0-lite", "1-lite"])
 def test_embedding_tp_weight_and_input_gradients_vs_autograd(seed):
     """the embedding tensor product (PairInteractionEmbeddingBlock.conv_tp, num_types x 0e input) through the same
