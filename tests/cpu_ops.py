@@ -121,7 +121,8 @@ def tp_fused(dp, srcs, rows, h2n=None, h2e=None, geo=None, tag="linear", gather=
     for r in res:
         if r is not None:
             out = out + _np(r)
-    if reduce is not None:                                     # the fused node scatter: run sums in slot order, added left to right as the kernel's scan does
+    if reduce is not None:                                     # the fused node scatter: every run summed in float64.  NOT the kernel's order -- its scan adds along a four-step
+                                                               # tree in float32 (csrc/tp_stage.h:is_seg_scan; restated in tests/emu.py:seg_scan) -- so this pins the host glue only
         eperm, run_id, R = _np(reduce[0]).astype(np.int64), _np(reduce[1]).astype(np.int64), int(reduce[2])
         part = np.zeros((R, out.shape[1]), out.dtype)
         np.add.at(part, run_id, out[eperm])

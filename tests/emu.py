@@ -587,3 +587,45 @@ def run_row_program(rp, x, res=(), dtype=np.float64):
         out += r
     assert np.isfinite(out).all()
     return out
+
+
+# ---- the fused node scatter of the input-stationary kernel's epilogue (csrc/tp_stage.h:is_scan_setup / is_seg_scan)
+
+def _row_shr(v, d):
+    """DPP row_shr:d over the 16 slots of a tile (axis 1) with bound_ctrl: slot el reads slot el - d, zero beyond the row's end"""
+    out = np.zeros_like(v)
+    out[:, d:] = v[:, :16 - d]
+    return out
+
+
+def _row_shl1(v):
+    out = np.zeros_like(v)
+    out[:, :15] = v[:, 1:]
+    return out
+
+
+def seg_scan_setup(rid):
+    """numpy twin of is_scan_setup: rid int [tiles, 16], the run id of every slot (a tail slot carries -1 - slot).  The four step masks are formed from the head
+    flags with the kernel's own shifts and `el < d` overrides (not from the run lengths).  Returns (m float32 [4, tiles, 16], last bool [tiles, 16])."""
+    rid = np.asarray(rid, dtype=np.int32)
+    assert rid.ndim == 2 and rid.shape[1] == 16
+    el = np.arange(16)[None, :]
+    prev, nxt = _row_shr(rid, 1), _row_shl1(rid)
+    f = ((el == 0) | (prev != rid)).astype(np.int32)                                # run head
+    last = (el == 15) | (nxt != rid)
+    f1 = f | np.where(el < 1, 1, _row_shr(f, 1))
+    f2 = f1 | np.where(el < 2, 1, _row_shr(f1, 2))
+    f4 = f2 | np.where(el < 4, 1, _row_shr(f2, 4))
+    m = np.stack([np.where(g != 0, 0.0, 1.0) for g in (f, f1, f2, f4)]).astype(np.float32)
+    return m, last
+
+
+def seg_scan(x, m):
+    """numpy twin of is_seg_scan: x float32 [tiles, 16, ...] -> the segmented inclusive sums along the slots, the four fused steps d = 1, 2, 4, 8 in float32
+    (a mask is 0.0 or 1.0, so fmaf(m, y, x) is the ONE rounded addition x + m y)"""
+    x = np.asarray(x)
+    assert x.dtype == np.float32 and x.shape[:2] == m.shape[1:]
+    mm = m.reshape(m.shape + (1,) * (x.ndim - 2))
+    for k, d in enumerate((1, 2, 4, 8)):
+        x = (mm[k] * _row_shr(x, d) + x).astype(np.float32)
+    return x

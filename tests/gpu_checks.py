@@ -1,5 +1,6 @@
 """GPU parity checks (HIP path through the C ABI vs the CPU oracle / committed golden fixtures).  Used by
 tests/test_gpu_parity.py (-m gpu) and by __graft_entry__.smoke().  Nothing here reads /root/reference."""
+import contextlib
 import json
 import math
 import os
@@ -760,11 +761,351 @@ def check_fused_scatter(device="cuda", n_atoms=14, seed=5):
     finally:
         os.environ.pop("HG_IS_PARTS", None)
         os.environ.pop("HG_FUSED_SCATTER", None)
-    from hamgnn_amd.topo import Topology
     out["node_rel_err"] = rel(reps["1"]["node_attr"], reps["0"]["node_attr"])
     out["edge_rel_err"] = rel(reps["1"]["edge_attr"], reps["0"]["edge_attr"])
     out["edges_mod_16"] = float(int(g.num_edges) % 16 == 0) * 1e-9
+    out.update(tile_statistics(g["edge_index"][1], int(g.num_nodes)))     # what the docstring promises, counted from the receivers themselves
     return out
+
+
+def tile_statistics(dst, N):
+    """how the receiver-sorted edges of a graph fall into 16-slot tiles, counted WITHOUT topo.Topology.receiver_major: the tail length E mod 16, the number of
+    receivers whose edges lie in more than one tile, the largest / smallest number of runs of equal receivers in a tile"""
+    recv = np.sort(np.asarray(dst.cpu() if torch.is_tensor(dst) else dst, dtype=np.int64), kind="stable")
+    E = int(recv.size)
+    if E == 0:
+        return {"E": 0, "tail_edges": 0, "straddling_receivers": 0, "runs_per_tile_max": 0, "runs_per_tile_min": 0}
+    tile = np.arange(E) // 16
+    first, last = np.full(N, E, dtype=np.int64), np.full(N, -1, dtype=np.int64)
+    np.minimum.at(first, recv, tile)
+    np.maximum.at(last, recv, tile)
+    head = np.ones(E, dtype=bool)
+    head[1:] = (recv[1:] != recv[:-1]) | (np.arange(1, E) % 16 == 0)
+    per_tile = np.bincount(tile[head])
+    return {"E": E, "tail_edges": E % 16, "straddling_receivers": int((last > first).sum()), "runs_per_tile_max": int(per_tile.max()), "runs_per_tile_min": int(per_tile.min())}
+
+
+# ---------------------------------------------------------------------------------------------- the fused node scatter on every run shape
+
+
+@contextlib.contextmanager
+def spy_tp_fused():
+    """records what every ops.tp_fused call inside the block asked for: kernel, workgroups per 16-edge tile, fused node scatter given"""
+    from hamgnn_amd import ops
+    launches, real = [], ops.tp_fused
+
+    def spy_fused(dp, srcs, rows, *a, **kw):
+        is_ = dp.sched is not None
+        launches.append(dict(op="tp_fused", tag=kw.get("tag", "linear"), rows=int(rows), kernel="is" if is_ else "seg", parts=dp.is_parts_for(int(rows)) if is_ else 0,
+                             fixed_parts=dp.fixed_parts, reduce=kw.get("reduce") is not None))
+        return real(dp, srcs, rows, *a, **kw)
+
+    ops.tp_fused = spy_fused
+    try:
+        yield launches
+    finally:
+        ops.tp_fused = real
+
+
+SENTINEL = -12345.0
+
+
+@contextlib.contextmanager
+def sentinel_empty():
+    """inside the block torch.empty hands out rows filled with SENTINEL, so that what a kernel did NOT write can be told from what it wrote;
+    yields a one-element list: the number of allocations served"""
+    real, calls = torch.empty, [0]
+
+    def filled(*a, **kw):
+        t = real(*a, **kw)
+        if t.is_floating_point():
+            calls[0] += 1
+            t.fill_(SENTINEL)
+        return t
+
+    torch.empty = filled
+    try:
+        yield calls
+    finally:
+        torch.empty = real
+
+
+def run_shape_cuts(which="all", seed=0):
+    """cuts of a 16-slot tile into runs as 15-bit numbers (bit s - 1: a run starts at slot s; slot 0 always starts one), in a fixed shuffled order.
+    "all": the 2^15 of them; an int n: cut 0 (one run), cut 0x7fff (16 runs) and a fixed-seed sample of n - 2 others"""
+    rng = np.random.default_rng(4242 + seed)
+    cuts = rng.permutation(1 << 15).astype(np.int64)
+    if which == "all":
+        return cuts
+    rest = cuts[(cuts != 0) & (cuts != 0x7fff)][:int(which) - 2]
+    return rng.permutation(np.concatenate([[0, 0x7fff], rest]))
+
+
+def run_shape_slots(cuts, drop=0):
+    """(head flag, run index) of every slot of the receiver-sorted edge list whose tile t is cut by cuts[t], with the last `drop` slots removed"""
+    cuts = np.asarray(cuts, dtype=np.int64)
+    head = np.ones((cuts.size, 16), dtype=bool)
+    head[:, 1:] = ((cuts[:, None] >> np.arange(15)[None, :]) & 1).astype(bool)
+    head = head.reshape(-1)
+    head = head[:head.size - drop]
+    return head, np.cumsum(head) - 1
+
+
+def fused_scatter_block(device="cuda", seed=0):
+    """a mini-irreps MessagePackBlock with seeded random weights, compiled once for the checks below, and the tables its launches need"""
+    from hamgnn_amd import nn as hnn, plan as P
+    torch.manual_seed(1234 + seed)
+    m = hnn.MessagePackBlock(MINI, MINI, SH, MINI, 8, [16, 16])
+    os.environ["HG_IS_PARTS"] = "1"
+    try:
+        m.compile(device, unrotate=True)
+    finally:
+        os.environ.pop("HG_IS_PARTS", None)
+    lay = P.PlanarLayout(MINI)
+    lm = max(P.Irreps(MINI).lmax, P.Irreps(SH).lmax)
+    imap_np = lay.index_map().astype(np.int64)
+    pad = np.setdiff1d(np.arange(lay.dim), imap_np)
+    assert pad.size > 0                                        # (the layout pads its channel groups: there ARE padding columns to watch)
+    return dict(m=m, lay=lay, lm=lm, D=int(imap_np.size), imap=torch.from_numpy(imap_np.astype(np.int32)).to(device), pad=torch.from_numpy(pad).to(device),
+                rot=torch.from_numpy(P.rotate_table(lay)).to(device), jtab=torch.from_numpy(P.wigner_jtab(lm)).to(device))
+
+
+def check_fused_scatter_all_run_shapes(device="cuda", cuts="all", drop=0, last_cut=None, seed=0, block=None):
+    """The segmented scan of the edge kernel's epilogue (csrc/tp_stage.h:is_scan_setup / is_seg_scan) in isolation, on EVERY way a 16-slot tile can be cut into runs.
+    One graph whose receiver-sorted edge list has tile t cut by cuts[t] (run_shape_cuts), every run with a receiver of its own, the edges stored in a shuffled order
+    (eperm is not the identity), random senders; last_cut replaces the cut of the last tile, drop removes the last `drop` edges of the sorted list (a ragged tail; the
+    receivers that lose all their edges stay as nodes without edges).  topo.Topology.receiver_major of that graph must reproduce the intended cuts exactly.
+    The same mini-irreps MessagePackBlock launch (single part forced, node rows gathered and rotated in the kernel: run_nodes) runs with reduce=(eperm, run_id, R) --
+    twice -- and without.  Reference: the unfused rows of each run summed in float64 on the device.  Bar, per element, no element excluded:
+        |fused - exact| <= 4.5 * 2^-24 * sum_i |x_i|    over the run's terms
+    (a four-step tree puts at most four rounded additions on the way of any term: gamma_4 = 4 u + O(u^2), u = 2^-24; the last half unit covers the cast of the
+    reference) -- derived, not measured.  Also counted: elements of single-edge runs that differ from the unfused row (must be 0: no addition happens), the largest
+    padding-channel value (must be 0.0), elements that differ between the two fused launches (0), and whether the two rows allocated BEHIND row R - 1 still hold the
+    sentinel they were filled with (no row >= R is written: tail slots carry ids -1 - slot and read a clamped edge)."""
+    from hamgnn_amd import ops
+    from hamgnn_amd.topo import Topology
+    import time
+    B = block if block is not None else fused_scatter_block(device, seed)
+    m = B["m"]
+    cuts = run_shape_cuts(cuts, seed) if isinstance(cuts, (str, int)) else np.asarray(cuts, dtype=np.int64)
+    if last_cut is not None:
+        cuts = np.concatenate([cuts[:-1], [int(last_cut)]])
+    rng = np.random.default_rng(77 + seed)
+    N = int(run_shape_slots(cuts)[1][-1]) + 1                  # one node per run of the complete list
+    head, run = run_shape_slots(cuts, drop)
+    E, R_want = int(head.size), int(run[-1]) + 1
+    slot_to_edge = rng.permutation(E)
+    dst = np.empty(E, dtype=np.int64)
+    dst[slot_to_edge] = run
+    src = rng.integers(0, N, size=E)
+    ei = torch.from_numpy(np.stack([src, dst])).to(device)
+    topo = Topology({"edge_index": ei, "z": torch.zeros(N, dtype=torch.long, device=device)})
+    eperm, run_id, R, prow, ident = topo.receiver_major()
+    # the graph IS the intended one: the same cuts, one output row per run, a permuted walk
+    assert R == R_want and np.array_equal(run_id.cpu().numpy().astype(np.int64), run), (R, R_want)
+    assert np.array_equal(dst[eperm.cpu().numpy()], run) and (E < 2 or bool((eperm.cpu() != torch.arange(E)).any()))
+    assert int(prow[-1]) == R and np.array_equal((prow[1:] - prow[:-1]).cpu().numpy()[:R], np.ones(R, dtype=np.int64))
+    stats = tile_statistics(dst, N)
+    assert stats["tail_edges"] == (16 - drop) % 16, stats
+
+    g = torch.Generator().manual_seed(900 + seed)
+    pl = lambda t: ops.to_planar(t.float().to(device), B["imap"], B["lay"].dim)
+    xs, xd, fe = pl(torch.randn(N, B["D"], generator=g)), pl(torch.randn(N, B["D"], generator=g)), pl(torch.randn(E, B["D"], generator=g))
+    vec = torch.randn(E, 3, generator=g) * 3.0
+    geo = ops.Geometry(torch.zeros(N, 3, device=device), ei, vec.float().to(device), 8.0, 8, B["lm"], B["jtab"])
+    geo.rbf = torch.randn(E, 8, generator=g).float().to(device).contiguous()
+    f_rot = ops.rotate_gather(fe, None, geo, B["rot"])
+    os.environ["HG_IS_PARTS"] = "1"
+    try:
+        with spy_tp_fused() as launches:
+            with sentinel_empty() as served:
+                fused = m.run_nodes(xs, xd, f_rot, geo, B["rot"], reduce=(eperm, run_id, R + 2))      # (the third entry only sizes the allocation: two rows to spare)
+                if device != "cpu":
+                    torch.cuda.synchronize()
+                t0 = time.time()
+                again = m.run_nodes(xs, xd, f_rot, geo, B["rot"], reduce=(eperm, run_id, R + 2))
+                if device != "cpu":
+                    torch.cuda.synchronize()
+                seconds = time.time() - t0
+            rows = m.run_nodes(xs, xd, f_rot, geo, B["rot"])
+    finally:
+        os.environ.pop("HG_IS_PARTS", None)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    assert tuple(fused.shape) == (R + 2, B["lay"].dim) and tuple(rows.shape) == (E, B["lay"].dim)
+    # rows >= R hold what the allocation gave them (the stand-ins of the CPU suite build their result by value: zeros, no allocation served)
+    spare_want = SENTINEL if served[0] else 0.0
+    spare_ok = bool((fused[R:] == spare_want).all()) and bool((again[R:] == spare_want).all())
+    fused, again = fused[:R], again[:R]
+    lens = torch.bincount(run_id.long(), minlength=R)
+    x = rows[eperm].double()
+    exact = torch.segment_reduce(x, "sum", lengths=lens, axis=0, unsafe=True)
+    sabs = torch.segment_reduce(x.abs(), "sum", lengths=lens, axis=0, unsafe=True)
+    del x
+    u = 2.0 ** -24
+    diff = (fused.double() - exact).abs()
+    over = int((~(diff <= 4.5 * u * sabs)).sum())              # (written so that a NaN counts as over the bar)
+    worst = float((diff / (u * sabs).clamp(min=1e-300)).max())
+    single = lens == 1
+    first = torch.cumsum(lens, 0) - lens
+    single_diff = int((fused[single] != rows[eperm[first[single]]]).sum())
+    return {"E": E, "tiles": int(cuts.size), "N": N, "R": R, "drop": drop, "tail_edges": stats["tail_edges"], "runs_per_tile_max": stats["runs_per_tile_max"],
+            "runs_per_tile_min": stats["runs_per_tile_min"], "launches": [(l["kernel"], l["parts"], l["reduce"]) for l in launches],
+            "elements": int(diff.numel()), "over_bar": over, "worst_in_units_of_u_sum_abs": worst, "finite": bool(torch.isfinite(fused).all()),
+            "single_edge_runs": int(single.sum()), "single_edge_elements_changed": single_diff,
+            "padding_max_abs": float(torch.maximum(fused[:, B["pad"]].abs().max(), rows[:, B["pad"]].abs().max())),
+            "repeat_elements_changed": int((fused != again).sum()), "spare_rows_intact": spare_ok, "sentinel_allocations": served[0],
+            "absmax": float(exact.abs().max()), "fused_launch_seconds": round(seconds, 4)}
+
+
+def assert_run_shapes(r, reduce_launches=2):
+    """the assertions of section 1 on one result of check_fused_scatter_all_run_shapes (the -m gpu tests, and the CPU suite's run through the stand-ins)"""
+    assert r["launches"] == [("is", 1, True)] * reduce_launches + [("is", 1, False)], r
+    assert r["finite"] and r["absmax"] > 0.1, r
+    assert r["over_bar"] == 0 and r["worst_in_units_of_u_sum_abs"] <= 4.5, r            # |fused - exact| <= 4.5 * 2^-24 * sum |x_i|, every element
+    assert r["single_edge_elements_changed"] == 0, r                                    # a run of one edge is the unfused row, bit for bit
+    assert r["padding_max_abs"] == 0.0, r
+    assert r["repeat_elements_changed"] == 0, r
+    assert r["spare_rows_intact"], r
+
+
+def scatter_graph(name, seed=0):
+    """(N, src, dst) of the small graphs that put run ends on, before and behind tile ends (the edges in a fixed shuffled order, random senders):
+    e1: one edge; one15 / one16 / one17: all edges on one receiver; sixteen: 16 edges on 16 receivers; drift: in-degrees 16, 16, 17, 15 (run ends coincide with tile
+    ends, then drift by one); hub: hub_graph() -- one atom with 40 incoming edges over three tiles, twenty atoms with one, node 0 and the last node with none"""
+    rng = np.random.default_rng(31 + seed)
+    if name == "hub":
+        g = hub_graph()
+        return int(g["z"].shape[0]), g["edge_index"][0].numpy().copy(), g["edge_index"][1].numpy().copy()
+    if name == "e1":
+        N, dst = 3, np.array([1])
+    elif name in ("one15", "one16", "one17"):
+        N, dst = 3, np.full(int(name[3:]), 1)
+    elif name == "sixteen":
+        N, dst = 16, np.arange(16)
+    elif name == "drift":
+        N, dst = 4, np.repeat(np.arange(4), [16, 16, 17, 15])
+    else:
+        raise ValueError(name)
+    dst = rng.permutation(dst.astype(np.int64))
+    return N, rng.integers(0, N, size=dst.size), dst
+
+
+SCATTER_GRAPHS = ("e1", "one15", "one16", "one17", "sixteen", "drift", "hub")
+
+
+def hub_graph(zs=(14, 8, 6, 1), seed=0):
+    """23 atoms in the graph format of hamgnn_amd.data.synthetic, every edge with its inverse: atom 8 is the hub -- 20 edges from its own periodic images (ten +- cell
+    shifts) and one from each of twenty satellites, 40 incoming edges that lie in three tiles of the receiver-sorted list (slots 7 .. 46) --, the satellites receive one
+    edge each (from the hub), atoms 0 and 22 have no edge at all.  60 edges: three full tiles and a 12-edge tail.  (The edge list is GIVEN, not every pair in range:
+    build_internal_graph is off in the models that read it.)"""
+    from hamgnn_amd.data import Graph
+    rng = np.random.default_rng(2024 + seed)
+    N, hub, L = 23, 8, 7.0
+    sat = [a for a in range(1, N - 1) if a != hub]
+    half = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, -1, 0), (1, 0, -1), (0, 1, -1), (1, 1, 1)]
+    cell = np.diag([L, L, L]) + rng.normal(0, 0.1, size=(3, 3))
+    pos = rng.uniform(-1.0, 1.0, size=(N, 3))
+    for a in sat + [0, N - 1]:
+        d = rng.normal(size=3)
+        pos[a] = pos[hub] + d / np.linalg.norm(d) * rng.uniform(3.0, 9.0)
+    edges = [(hub, hub, s) for h in half for s in (h, tuple(-c for c in h))]
+    edges += [(a, hub, (0, 0, 0)) for a in sat] + [(hub, a, (0, 0, 0)) for a in sat]
+    edges.sort(key=lambda e: (e[0], e[1], e[2]))              # centre-major like the generators of hamgnn_amd.data.synthetic
+    where = {e: k for k, e in enumerate(edges)}
+    inv = np.array([where[(j, i, tuple(-c for c in s))] for i, j, s in edges], dtype=np.int64)
+    src, dst = np.array([e[0] for e in edges], dtype=np.int64), np.array([e[1] for e in edges], dtype=np.int64)
+    sh = np.array([e[2] for e in edges], dtype=np.int64)
+    z = rng.choice(np.asarray(zs), size=N)
+    return Graph(z=torch.from_numpy(z.astype(np.int64)), pos=torch.from_numpy(pos.astype(np.float32)), cell=torch.from_numpy(cell.astype(np.float32))[None],
+                 edge_index=torch.from_numpy(np.stack([src, dst])), cell_shift=torch.from_numpy(sh), nbr_shift=torch.from_numpy((sh @ cell).astype(np.float32)),
+                 inv_edge_idx=torch.from_numpy(inv), batch=torch.zeros(N, dtype=torch.long), node_counts=torch.tensor([N]))
+
+
+def check_message_pack_nodes_forward(device="cuda", graph="hub", seed=0, irr=None, sh=None, radial=(16, 16), parts=None, reduce=False):
+    """The forward launch of a ConvBlock as the backbone issues it -- MessagePackBlock.run_nodes: NODE rows gathered by sender / receiver and rotated inside the kernel --
+    on the graphs of scatter_graph(), against the fp64 oracle's MessagePackBlock on node[src], node[dst]; with reduce, the fused node scatter
+    (reduce=(eperm, run_id, R) of topo.Topology.receiver_major, then ops.segment_sum over each node's rows) against index_add of the oracle's rows onto the receivers.
+    Random irreps set unless given.  parts: workgroups per 16-edge tile forced (HG_IS_PARTS).  The result states what the launch asked for (kernel, parts_used,
+    reduce_ran -- recorded from the ops.tp_fused call itself).  A program whose LDS tiles fix several workgroups per tile (`fixed_parts == "lds"`) cannot take the
+    fused scatter: reported as reduce_skipped, nothing compared."""
+    from oracle import hamgnn_ref as R, e3
+    from hamgnn_amd import nn as hnn, ops, plan as P
+    from hamgnn_amd.topo import Topology
+    from tests.test_plan_emu import _random_irreps
+    rng = np.random.default_rng(100 + seed)
+    if irr is None:
+        lmax = int(rng.integers(1, 4))
+        irr = _random_irreps(rng, lmax)
+        if "0e" not in irr:
+            irr = "5x0e+" + irr
+        lsh = int(rng.integers(1, 4))
+        sh = "+".join(f"{l}{'e' if l % 2 == 0 else 'o'}" for l in range(lsh + 1))
+    lmax, lsh = P.Irreps(irr).lmax, P.Irreps(sh).lmax
+    N, src_np, dst_np = scatter_graph(graph)
+    E = int(dst_np.size)
+    s_, r_ = torch.from_numpy(src_np), torch.from_numpy(dst_np)
+    torch.manual_seed(seed)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        ref = R.MessagePackBlock(irr, irr, sh, irr, "8x0e", radial_MLP=list(radial))
+        g = torch.Generator().manual_seed(seed)
+        D = ref.irreps_node_feats.dim
+        xs, xd, ef = torch.randn(N, D, generator=g), torch.randn(N, D, generator=g), torch.randn(E, D, generator=g)
+        vec = torch.randn(E, 3, generator=g) * 3.0
+        n = torch.nn.functional.normalize(vec, dim=-1)
+        shv = e3.spherical_harmonics(list(range(lsh + 1)), n, True, "component")
+        rbf = torch.randn(E, 8, generator=g)
+        with torch.no_grad():
+            want = ref(xs[s_], xd[r_], ef, shv, rbf)
+            if reduce:
+                want = torch.zeros(N, D).index_add_(0, r_, want)
+    finally:
+        torch.set_default_dtype(prev)
+    m = load_weights(hnn.MessagePackBlock(irr, irr, sh, irr, 8, list(radial)), {k: v.detach().numpy() for k, v in ref.state_dict().items()})
+    lay = P.PlanarLayout(irr)
+    lm = max(lmax, lsh)
+    v = torch.stack([n[:, 2], n[:, 0], n[:, 1]], 1) * 2.0          # e3nn axis order (y, z, x) -> physical (x, y, z)
+    jtab = torch.from_numpy(P.wigner_jtab(lm)).to(device)
+    ei = torch.stack([s_, r_]).to(device)
+    imap = torch.from_numpy(lay.index_map().astype(np.int32)).to(device)
+    rot = torch.from_numpy(P.rotate_table(lay)).to(device)
+    pl = lambda t: ops.to_planar(t.float().to(device), imap, lay.dim)
+    res = {"graph": graph, "E": E, "N": N, "irreps": irr, "sh": sh, "reduce_asked": bool(reduce), "reduce_skipped": False}
+    if parts is not None:
+        os.environ["HG_IS_PARTS"] = str(parts)
+    try:
+        m.compile(device, unrotate=True)
+        geo = ops.Geometry(torch.zeros(N, 3, device=device), ei, v.float().to(device), 8.0, 8, lm, jtab)
+        geo.rbf = rbf.float().to(device).contiguous()
+        f_rot = ops.rotate_gather(pl(ef), None, geo, rot)
+        dp = m._dp_for(E)
+        res.update(fixed_parts=dp.fixed_parts, compiled="is" if m._dp.sched is not None else "seg")
+        if reduce and dp.fixed_parts == "lds":
+            res.update(reduce_skipped=True, kernel="is", parts_used="lds", reduce_ran=False, rel_err=None)
+            return res
+        with spy_tp_fused() as launches:
+            if reduce:
+                topo = Topology({"edge_index": ei, "z": torch.zeros(N, dtype=torch.long, device=device)})
+                eperm, run_id, R_, prow, ident = topo.receiver_major()
+                part = m.run_nodes(pl(xs), pl(xd), f_rot, geo, rot, reduce=(eperm, run_id, R_))
+                assert tuple(part.shape) == (R_, lay.dim)
+                y = ops.segment_sum(part, prow, ident, N)
+                res.update(R=R_, **{k: v_ for k, v_ in tile_statistics(r_, N).items() if k != "E"})
+            else:
+                y = m.run_nodes(pl(xs), pl(xd), f_rot, geo, rot)
+    finally:
+        if parts is not None:
+            os.environ.pop("HG_IS_PARTS", None)
+    y = ops.from_planar(y, imap)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    (l,) = launches                                            # ONE edge-kernel launch did the work
+    scale = want.abs().max().item()
+    part_rows = int(dp.is_tables(l["parts"])[0].part_table.shape[0]) if l["kernel"] == "is" else 0      # (a program with fewer output segments than parts asked for runs one per segment)
+    res.update(kernel=l["kernel"], parts_used=l["parts"], part_rows=part_rows, reduce_ran=l["reduce"], rel_err=0.0 if scale < 1e-12 else rel(y, want))
+    return res
 
 
 def check_structural_zeros(device="cuda", legacy=False, n_atoms=9, seed=11):
@@ -1383,8 +1724,11 @@ def check_head_su2(device="cuda"):
 
 
 def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, nao=19, num_layers=2, radial=(16, 16), num_radial=8,
-                         n_graphs=1, legacy_edge_update=False, zs=(14, 8, 6, 1), soc=False, isolated=False):
-    """Seeded random weights on a synthetic periodic cell: full backbone + head, HIP (fp32) vs oracle (fp64, CPU)."""
+                         n_graphs=1, legacy_edge_update=False, zs=(14, 8, 6, 1), soc=False, isolated=False, graph=None, parts=None):
+    """Seeded random weights on a synthetic periodic cell: full backbone + head, HIP (fp32) vs oracle (fp64, CPU).
+    graph="hub": hub_graph() instead of a random cell (one receiver over three tiles, single-edge receivers, atoms without edges, a ragged tail).
+    parts: workgroups per 16-edge tile forced for every input-stationary launch (HG_IS_PARTS; 1 = the large-graph launches with the node scatter fused into the
+    ConvBlocks' edge kernel); the message-block launches the forward issued are then in the result (`launches`)."""
     from oracle import hamgnn_ref as R
     from hamgnn_amd.data import synthetic as S
     from hamgnn_amd.models.hamgnn_conv import HamGNNConvE3
@@ -1401,8 +1745,13 @@ def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, n
         ref_head = R.HamGNNPlusPlusOut(irreps, irreps, nao_max=nao, ham_type="openmx", symmetrize=True, add_H0=True, soc_switch=soc)
     finally:
         torch.set_default_dtype(prev)
-    gs = [S.add_random_targets(S.random_cell(n_atoms + 2 * k, list(zs), seed=seed + k, density=0.004), nao, seed=seed + k, soc=soc)
-          for k in range(n_graphs)]
+    if graph == "hub":
+        assert n_graphs == 1
+        gs = [S.add_random_targets(hub_graph(zs, seed), nao, seed=seed, soc=soc)]
+    else:
+        assert graph is None, graph
+        gs = [S.add_random_targets(S.random_cell(n_atoms + 2 * k, list(zs), seed=seed + k, density=0.004), nao, seed=seed + k, soc=soc)
+              for k in range(n_graphs)]
     if isolated:                                              # a crystal WITHOUT edges in the middle of the batch (one atom, no neighbour in range)
         gs.insert(1, S.add_random_targets(S.random_cell(1, [int(zs[0])], seed=seed, density=1e-6), nao, seed=seed, soc=soc))
         assert gs[1].num_edges == 0
@@ -1415,15 +1764,24 @@ def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, n
     hip_head = load_weights(HamGNNPlusPlusOut(irreps, irreps, nao_max=nao, ham_type="openmx", ham_only=True, symmetrize=True, add_H0=True,
                                               soc_switch=soc), {k: v for k, v in ref_head.state_dict().items()})
     g64 = type(g)({k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in g.items()})
-    with torch.no_grad():
-        rep_ref = ref(g64)
-        H_ref = ref_head(g64, rep_ref)["hamiltonian"]
-        gd = g.to(device)
-        rep = hip(gd)
-        H = hip_head(gd, rep)["hamiltonian"]
+    if parts is not None:
+        os.environ["HG_IS_PARTS"] = str(parts)
+    try:
+        with torch.no_grad(), spy_tp_fused() as launches:
+            rep_ref = ref(g64)
+            H_ref = ref_head(g64, rep_ref)["hamiltonian"]
+            gd = g.to(device)
+            rep = hip(gd)
+            H = hip_head(gd, rep)["hamiltonian"]
+    finally:
+        if parts is not None:
+            os.environ.pop("HG_IS_PARTS", None)
     torch.cuda.synchronize()
-    return {"E": g.num_edges, "node_rel_err": rel(rep["node_attr"], rep_ref["node_attr"]), "edge_rel_err": rel(rep["edge_attr"], rep_ref["edge_attr"]),
-            "H_rel_err": rel(H, H_ref), "H_mae": (H.double().cpu() - H_ref).abs().mean().item()}
+    out = {"E": g.num_edges, "node_rel_err": rel(rep["node_attr"], rep_ref["node_attr"]), "edge_rel_err": rel(rep["edge_attr"], rep_ref["edge_attr"]),
+           "H_rel_err": rel(H, H_ref), "H_mae": (H.double().cpu() - H_ref).abs().mean().item()}
+    if parts is not None:
+        out["launches"] = [l for l in launches if l["tag"] == "message_pack"]
+    return out
 
 
 def check_default_irreps_si2(device="cuda", which="A", graph="si2", soc=False):

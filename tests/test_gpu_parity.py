@@ -73,6 +73,8 @@ def test_fused_node_scatter_equals_message_rows_plus_segment_sum():
     print(r)
     # (two summation orders of the receivers' sums: G.SAME_MATH_TOL; the edge rows downstream inherit the node rows' rounding)
     assert r["node_rel_err"] < G.SAME_MATH_TOL and r["edge_rel_err"] < G.SAME_MATH_TOL, r
+    # what the check's docstring promises did occur: a ragged tail, receivers whose edges lie in more than one tile (14 atoms, seed 5: 474 edges, a 10-edge tail)
+    assert r["tail_edges"] > 0 and r["straddling_receivers"] > 0, r
 
 
 @pytest.mark.parametrize("legacy", [False, True])
