@@ -69,6 +69,8 @@ class _BackboneBase(nn.Module):
     """What HamGNNConvE3 and HamGNNTransformer share (hamgnn_conv.py:89-190 == hamgnn_transformer.py:37-112): config keys, atomic /
     pair / chemical embedding, per-edge geometry, and the lazily converted result dict."""
 
+    _kan_built = False                                         # which backbones run HamGNN_pre.use_kan (the others refuse it in _init_common)
+
     def _structural_zero_sets(self):
         """(node irreps, edge irreps) that are STRUCTURALLY zero in the rows the first layer reads: the chemical embedding is an o3.Linear from
         `num_types x 0e` (toolbox/nequip/nn/_atomwise.py:55-57; charge doping adds to the same 0e attributes) -- only 0e blocks of the node rows can be
@@ -98,9 +100,14 @@ class _BackboneBase(nn.Module):
         if self.rbf_func not in ("bessel", "gaussian"):
             raise ValueError(f"Unsupported radial basis function: {g('rbf_func')}")      # hamgnn_conv.py:139-141
         self.lite_mode = bool(g("lite_mode", False))
-        for k in ("use_kan", "build_internal_graph"):
-            if g(k, False):
-                raise NotImplementedError(f"HamGNN_pre.{k}=True is outside the MI355X hot-path scope of this round (SURVEY 8f)")
+        if g("build_internal_graph", False):
+            raise NotImplementedError("HamGNN_pre.build_internal_graph=True is outside the MI355X hot-path scope of this round (SURVEY 8f)")
+        # use_kan: every radial weight generator is a B-spline KAN (message_passing.py:184-185, tensor_products.py:163-164) -- forward only, HamGNNConvE3 only
+        self.use_kan = bool(g("use_kan", False))
+        if self.use_kan and not self._kan_built:
+            raise NotImplementedError(f"HamGNN_pre.use_kan=True is not built for {type(self).__name__} (HamGNNConvE3 runs it)")
+        if self.use_kan and len(self.radial_MLP) > P.KAN_MAX_HIDDEN_LAYERS:
+            raise NotImplementedError(f"HamGNN_pre.use_kan=True with a radial_MLP of {len(self.radial_MLP)} entries: at most {P.KAN_MAX_HIDDEN_LAYERS} are built")
         # use_gradient_checkpointing (hamgnn_conv.py:40-85, 236-246: torch.utils.checkpoint around every layer) is accepted and has nothing to
         # switch: the backward here keeps ONLY the layer inputs (forward(save_for_backward=True): node rows, edge rows, aggregates) and
         # re-evaluates every intermediate inside the block backwards -- the memory profile the reference's flag buys
@@ -114,7 +121,7 @@ class _BackboneBase(nn.Module):
             assert p == (-1) ** l
         D, sh, R, mlp = self.irreps_node_features, self.irreps_edge_sh, self.num_radial, self.radial_MLP
         self.lmax = max(D.lmax, sh.lmax)
-        self.pair_embedding = hnn.PairInteractionEmbeddingBlock(self.num_types, sh, D, R, mlp, self.lite_mode)
+        self.pair_embedding = hnn.PairInteractionEmbeddingBlock(self.num_types, sh, D, R, mlp, self.lite_mode, self.use_kan)
         self.chemical_embedding = nn.Module()
         self.chemical_embedding.linear = hnn.E3Linear(Irreps([(self.num_types, 0, 1)]), D)
         self.layout = P.PlanarLayout(D)
@@ -157,7 +164,10 @@ class _BackboneBase(nn.Module):
         topo.check_num_types(self.num_types)                   # z >= num_types would index past the embedding tables on the device
         geo = ops.Geometry(data.pos, data.edge_index, data.nbr_shift, self.cutoff, self.num_radial, self.lmax, self._jtab, self.rbf_func)
         # hidden activations of ALL radial weight generators of this forward (embedding + two per message block) in one launch
-        ops.prefill_radial_hidden(geo, self._radial_generators(), float(P.ACT_CONSTS[P.ACT_SILU]))
+        if self.use_kan:
+            ops.prefill_kan_hidden(geo, self._radial_generators())
+        else:
+            ops.prefill_radial_hidden(geo, self._radial_generators(), float(P.ACT_CONSTS[P.ACT_SILU]))
         Dp = self.layout.dim
         delta = None
         if self.apply_charge_doping:                           # node_attrs = one_hot(z) + delta (toolbox/nequip/nn/embedding/_embedding_block.py:124-131)
@@ -316,6 +326,8 @@ class _BackboneBase(nn.Module):
 
 
 class HamGNNConvE3(_BackboneBase):
+    _kan_built = True
+
     def __init__(self, config):
         super().__init__()
         self.use_corr_prod = bool(_cfg_get(_cfg_get(config, "HamGNN_pre", config), "use_corr_prod", False))
@@ -327,9 +339,9 @@ class HamGNNConvE3(_BackboneBase):
             self.corr_products = nn.ModuleList([hnn.CorrProductBlock(D, int(g("num_hidden_features")), int(g("correlation")), self.num_types, True)
                                                 for _ in range(self.num_layers)])
         for i in range(self.num_layers):
-            self.convolutions.append(hnn.ConvBlockE3(D, sh, R, mlp, self.lite_mode))
+            self.convolutions.append(hnn.ConvBlockE3(D, sh, R, mlp, self.lite_mode, self.use_kan))
             skip = (i > 0) if self.legacy_edge_update else True
-            self.pair_interactions.append(hnn.PairInteractionBlock(D, sh, R, mlp, skip, self.legacy_edge_update, self.lite_mode))
+            self.pair_interactions.append(hnn.PairInteractionBlock(D, sh, R, mlp, skip, self.legacy_edge_update, self.lite_mode, self.use_kan))
         self._mark_structural_zeros()
 
     def _mark_structural_zeros(self):
@@ -364,7 +376,7 @@ class HamGNNConvE3(_BackboneBase):
         dev = self._compiled_for
         if dev is None:
             return
-        if self.lite_mode:
+        if self.lite_mode or self.use_kan:
             self._compiled_for = None                          # full recompile on the next forward
             return
         if self.use_corr_prod:
@@ -380,6 +392,8 @@ class HamGNNConvE3(_BackboneBase):
 
     def forward(self, data, save_for_backward: bool = False):
         """save_for_backward: keep the layer inputs (node rows, edge rows, aggregated messages) on the result (`_tape`) for `backward`"""
+        if save_for_backward and self.use_kan:
+            raise NotImplementedError("HamGNN_pre.use_kan=True: training (forward(save_for_backward=True), backward, training_step) is not built")
         z, topo, geo, node, f = self._embed(data)
         N = z.shape[0]
         if os.environ.get("HG_CHECK_STRUCT_ZEROS") == "1":     # (tests) the blocks the first layer's programs treat as structural zeros ARE zero
@@ -444,6 +458,8 @@ class HamGNNConvE3(_BackboneBase):
         linear_up adjoints, the fused skip o3.Linear)  ->  ResidualBlock  ->  skip o3.Linear  ->  ConvBlockE3's message block with the
         receiver scatter's adjoint (a gather) fused into its staging;  then the pair embedding and the chemical embedding table.
         Returns {reference parameter name: gradient in the reference's layout}.  Non-lite, no CorrProduct, no charge doping, one rank."""
+        if self.use_kan:
+            raise NotImplementedError("HamGNN_pre.use_kan=True: the backward of the backbone is not built (the KAN weight generators run forward only)")
         if parallel.is_sharded(data) and self.apply_charge_doping:
             raise NotImplementedError("backbone backward of an edge-sharded graph with charge doping")
         tape = rep["_tape"]

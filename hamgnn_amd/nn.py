@@ -173,6 +173,61 @@ class FullyConnectedNet(nn.Module):
         return out
 
 
+KAN_GRID_SIZE, KAN_GRID_RANGE, KAN_SPLINE_ORDER = 3, (-1.0, 1.0), 3      # the reference's constants (utils/macro.py; efficient_kan's spline order)
+
+
+class _KANLinear(nn.Module):
+    """KANLinear parameter holder (toolbox/efficient_kan/kan.py:6-54): the reference's names and shapes, `grid` a buffer"""
+
+    def __init__(self, h_in, h_out, grid_size, grid_range):
+        super().__init__()
+        k = KAN_SPLINE_ORDER
+        step = (grid_range[1] - grid_range[0]) / grid_size
+        self.register_buffer("grid", (torch.arange(-k, grid_size + k + 1) * step + grid_range[0]).expand(h_in, -1).contiguous())
+        bound = 1.0 / math.sqrt(h_in)
+        self.base_weight = nn.Parameter((torch.rand(h_out, h_in) * 2 - 1) * bound)
+        self.spline_weight = nn.Parameter((torch.rand(h_out, h_in, grid_size + k) - 0.5) * (0.1 / grid_size))
+        self.spline_scaler = nn.Parameter((torch.rand(h_out, h_in) * 2 - 1) * bound)
+
+
+class KANNet(nn.Module):
+    """B-spline KAN weight generator (HamGNN_pre.use_kan: message_passing.py:184-185, tensor_products.py:163-164): parameter holder with the reference's
+    state-dict names `layers.{i}.{grid, base_weight, spline_weight, spline_scaler}`.  The hidden part runs in csrc/kan.hip, the last layer inside the edge
+    kernels (plan.kan_last_layer); forward only."""
+
+    def __init__(self, hs, grid_size=KAN_GRID_SIZE, grid_range=KAN_GRID_RANGE):
+        super().__init__()
+        self.hs = list(hs)
+        if len(self.hs) - 2 > P.KAN_MAX_HIDDEN_LAYERS:
+            raise NotImplementedError(f"use_kan=True with a radial_MLP of {len(self.hs) - 2} entries: at most {P.KAN_MAX_HIDDEN_LAYERS} are built")
+        self.layers = nn.ModuleList([_KANLinear(a, b, grid_size, grid_range) for a, b in zip(self.hs, self.hs[1:])])
+
+    def hidden_layers(self, device):
+        """-> ops.KanGenerator: every layer but the last, packed and uploaded"""
+        sd = {"g." + k: v.detach().cpu().double().numpy() for k, v in self.state_dict().items()}
+        return ops.KanGenerator(P.kan_layers(sd, "g"), device)
+
+
+def _weight_generator(hs, use_kan: bool):
+    return KANNet(hs) if use_kan else FullyConnectedNet(hs)
+
+
+def _hidden_rows(geo, gen):
+    """the rows the edge kernels multiply with the last generator layer: the hidden activations of a FullyConnectedNet, or Phi of a KAN"""
+    if isinstance(gen, ops.KanGenerator):
+        return ops.kan_hidden_cached(geo, gen)
+    return ops.radial_hidden_cached(geo, gen, float(P.ACT_CONSTS[P.ACT_SILU]))
+
+
+def _hidden_width(gen) -> int:
+    return gen.width if isinstance(gen, ops.KanGenerator) else gen[-1].shape[1]
+
+
+def _no_kan_backward(use_kan: bool, what: str):
+    if use_kan:
+        raise NotImplementedError(f"use_kan=True: {what} is not built (the KAN weight generators run forward only)")
+
+
 class _LinOutHolder(nn.Module):
     def __init__(self, tp: E3TensorProduct, irreps_out: Irreps):
         super().__init__()
@@ -218,9 +273,10 @@ def _wgrad_runner(wg, dpA, dpB):
 
 class MessagePackBlock(nn.Module):
     def __init__(self, irreps_node_feats, irreps_edge_feats, irreps_local_env_edge, irreps_out, num_radial, radial_MLP=(64, 64),
-                 lite_mode=False):
+                 lite_mode=False, use_kan=False):
         super().__init__()
         self.lite_mode = lite_mode
+        self.use_kan = bool(use_kan)
         self.irreps_node, self.irreps_edge = Irreps(irreps_node_feats), Irreps(irreps_edge_feats)
         self.irreps_sh, self.irreps_out = Irreps(irreps_local_env_edge), Irreps(irreps_out)
         comb = Irreps([(max(1, 2 * m), l, p) for m, l, p in self.irreps_node])
@@ -228,14 +284,14 @@ class MessagePackBlock(nn.Module):
             self.node_linear_scaler = _MidLinear(comb, self.irreps_sh, self.irreps_out)
             self.edge_linear_scaler = _MidLinear(self.irreps_edge, self.irreps_sh, self.irreps_out)
             self.combine_messages = _CombineMessages(self.irreps_out)
-            self.weight_generator_combine = FullyConnectedNet([num_radial] + list(radial_MLP) + [self.combine_messages.weight_numel])
+            self.weight_generator_combine = _weight_generator([num_radial] + list(radial_MLP) + [self.combine_messages.weight_numel], self.use_kan)
         else:
             self.node_tensor_product = E3TensorProduct(comb, self.irreps_sh, self.irreps_out)
             self.edge_tensor_product = E3TensorProduct(self.irreps_edge, self.irreps_sh, self.irreps_out)
             self.node_linear_scaler = LinearScaleWithWeights(self.node_tensor_product, self.irreps_out)
             self.edge_linear_scaler = LinearScaleWithWeights(self.edge_tensor_product, self.irreps_out)
-            self.node_weight_generator = FullyConnectedNet([num_radial] + list(radial_MLP) + [self.node_linear_scaler.weight_numel])
-            self.edge_weight_generator = FullyConnectedNet([num_radial] + list(radial_MLP) + [self.edge_linear_scaler.weight_numel])
+            self.node_weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.node_linear_scaler.weight_numel], self.use_kan)
+            self.edge_weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.edge_linear_scaler.weight_numel], self.use_kan)
             self.node_linear_out = E3Linear(self.irreps_out, self.irreps_out)
             self.edge_linear_out = E3Linear(self.irreps_out, self.irreps_out)
         self._dp = None
@@ -308,7 +364,7 @@ class MessagePackBlock(nn.Module):
             if sched != "seg" and os.environ.get("HG_MP_MERGE", "1") != "0":
                 # input-stationary kernel with the small output irreps sharing MFMA row tiles (plan.choose_merge_groups): -5 % MFMAs, -17 %
                 # items for set-A.  Such a program has no segment-stationary form: if it does not fit, fall back to the plain program.
-                groups = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, self._hn[-1].shape[1])
+                groups = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, _hidden_width(self._hn))
                 if groups:
                     try:
                         prog = P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate,
@@ -318,7 +374,7 @@ class MessagePackBlock(nn.Module):
                         if zkw:                                # the same block for rows whose marked irreps are structurally zero (first layer of a backbone) /
                             gz = groups                        # whose marked output irreps nobody reads (last PairInteractionBlock): those leave the row-tile groups
                             if zkw.get("dead_out"):
-                                gz = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, self._hn[-1].shape[1], dead_out=zkw["dead_out"])
+                                gz = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, _hidden_width(self._hn), dead_out=zkw["dead_out"])
                             self._groups_z = gz
                             self._dp_z = ops.DeviceProgram(P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate,
                                                                                        skip_weight, merge_groups=gz, **zkw), device, schedule="is")
@@ -344,7 +400,7 @@ class MessagePackBlock(nn.Module):
         """skip: the flat weight of the fused skip o3.Linear (device tensor) if the block was compiled with one.  Returns False when
         there is nothing to refresh in place (never compiled, lite_mode): the caller compiles instead."""
         from . import repack as RP
-        if self.lite_mode or self._dp is None or getattr(self, "_compile_args", None) is None:
+        if self.lite_mode or self.use_kan or self._dp is None or getattr(self, "_compile_args", None) is None:
             return False
         unrotate, has_skip, groups = self._compile_args
         if has_skip != (skip is not None):
@@ -420,6 +476,7 @@ class MessagePackBlock(nn.Module):
     def compile_adjoint(self, device, structural_zeros: bool = False):
         """upload the data-gradient program of this block (plan.build_message_pack_adjoint_program): same kernels, same weights.  structural_zeros: the
         variant that does not compute the gradient of the structurally zero input irreps (set_structural_zeros; nobody reads it)"""
+        _no_kan_backward(self.use_kan, "the data gradient of a MessagePackBlock")
         if self.lite_mode:
             raise NotImplementedError("data gradient of a lite_mode MessagePackBlock")
         zin = self._zero_inputs_kw() if structural_zeros else {}
@@ -440,6 +497,7 @@ class MessagePackBlock(nn.Module):
         kernel's staging like the forward's node gathers).  Returns per-edge gradients (g_src_rows, g_dst_rows, g_edge_rows), planar:
         the first two in the GLOBAL frame, to be summed over the edges of each sender / receiver (ops.segment_sum over the sender /
         receiver CSR) for the gradient of the gathered node rows; the third in the edge frame, where the forward read the edge rows."""
+        _no_kan_backward(self.use_kan, "the data gradient of a MessagePackBlock")
         z = bool(structural_zeros and self._zero_inputs_kw())   # (the caller vouches as for run_nodes: the marked input irreps are zero, their gradient unread)
         slot = "_dp_adj_z" if z else "_dp_adj"
         if getattr(self, slot, None) is None:
@@ -487,6 +545,7 @@ class MessagePackBlock(nn.Module):
         node_s / node_d: planar NODE rows gathered by sender / receiver as in run_nodes; f_rot: planar edge rows (edge frame).
         Returns {reference parameter name: gradient in the reference's flat layout}."""
         from . import backward_mp as BM
+        _no_kan_backward(self.use_kan, "the weight gradient of a MessagePackBlock")
         if self.lite_mode:
             raise NotImplementedError("weight gradients of a lite_mode MessagePackBlock")
         dev = grad_out.device
@@ -537,6 +596,7 @@ class MessagePackBlock(nn.Module):
         as backward_data / backward_weights.  lite_mode blocks go through hamgnn_amd/backward_lite.py (nothing large to materialise).
         structural_zeros: as run_nodes -- the caller vouches that the input irreps marked by set_structural_zeros are zero in the rows it passes AND that
         it does not read their gradient (a backbone's first layer): weight gradients of the paths that read them are exactly zero and not computed."""
+        _no_kan_backward(self.use_kan, "the backward of a MessagePackBlock")
         if not self.lite_mode:
             grads = self.backward_weights(node_s, node_d, f_rot, geo, rot_tab, grad_out, out_is_global, chunk=chunk, gather=gather, structural_zeros=structural_zeros)
             return self.backward_data(grad_out, geo, out_is_global, gather=gather, structural_zeros=structural_zeros) + (grads,)
@@ -572,9 +632,8 @@ class MessagePackBlock(nn.Module):
 
     def run(self, xs_rot, xd_rot, f_rot, geo: ops.Geometry):
         """xs_rot/xd_rot/f_rot: planar rows in the edge-aligned frame.  Returns planar [E, Dp] (global frame if unrotate)."""
-        cst = float(P.ACT_CONSTS[P.ACT_SILU])
-        hn = ops.radial_hidden_cached(geo, self._hn, cst)
-        he = ops.radial_hidden_cached(geo, self._he, cst) if self._he is not None else None
+        hn = _hidden_rows(geo, self._hn)
+        he = _hidden_rows(geo, self._he) if self._he is not None else None
         return ops.tp_fused(self._dp_for(geo.E), [xs_rot, xd_rot, f_rot], geo.E, hn, he, geo, tag="message_pack")
 
     def can_reduce(self, rows: int) -> bool:
@@ -588,9 +647,8 @@ class MessagePackBlock(nn.Module):
         if self._dp.sched is None:
             xs, xd = ops.rotate_gather(node_s, geo.src, geo, rot_tab, x2=node_d, idx2=geo.dst)
             return self.run(xs, xd, f_rot, geo)
-        cst = float(P.ACT_CONSTS[P.ACT_SILU])
-        hn = ops.radial_hidden_cached(geo, self._hn, cst)
-        he = ops.radial_hidden_cached(geo, self._he, cst) if self._he is not None else None
+        hn = _hidden_rows(geo, self._hn)
+        he = _hidden_rows(geo, self._he) if self._he is not None else None
         return ops.tp_fused(self._dp_for(geo.E, structural_zeros), [node_s, node_d, f_rot], geo.E, hn, he, geo, tag="message_pack", gather=[geo.src, geo.dst, None],
                             rot_mask=0b011, reduce=reduce)
 
@@ -689,10 +747,10 @@ class ResidualBlock(nn.Module):
 
 
 class ConvBlockE3(nn.Module):
-    def __init__(self, irreps, irreps_sh, num_radial, radial_MLP, lite_mode=False):
+    def __init__(self, irreps, irreps_sh, num_radial, radial_MLP, lite_mode=False, use_kan=False):
         super().__init__()
         self.residual = ResidualBlock(irreps, irreps)
-        self.conv_tp = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP, lite_mode)
+        self.conv_tp = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP, lite_mode, use_kan)
         self.skip_linear = E3Linear(irreps, irreps)
 
     def compile(self, device):
@@ -817,12 +875,12 @@ class AttentionBlockE3(nn.Module):
 
 
 class PairInteractionBlock(nn.Module):
-    def __init__(self, irreps, irreps_sh, num_radial, radial_MLP, use_skip_connections=True, legacy_edge_update=False, lite_mode=False):
+    def __init__(self, irreps, irreps_sh, num_radial, radial_MLP, use_skip_connections=True, legacy_edge_update=False, lite_mode=False, use_kan=False):
         super().__init__()
         self.use_skip_connections, self.legacy_edge_update, self.lite_mode = use_skip_connections, legacy_edge_update, lite_mode
         self.linear_up_src = E3Linear(irreps, irreps)
         self.linear_up_tar = E3Linear(irreps, irreps)
-        self.conv_tp = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP, lite_mode)
+        self.conv_tp = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP, lite_mode, use_kan)
         if use_skip_connections:
             self.skip_linear = E3Linear(irreps, irreps)
 
@@ -878,7 +936,7 @@ class PairInteractionBlock(nn.Module):
 class _EmbTP(nn.Module):
     """TensorProductWithMemoryOptimizationWithWeight parameter holder (tensor_products.py:51-189)."""
 
-    def __init__(self, irreps_in, irreps_sh, irreps_out, num_radial, radial_MLP, lite_mode=False):
+    def __init__(self, irreps_in, irreps_sh, irreps_out, num_radial, radial_MLP, lite_mode=False, use_kan=False):
         super().__init__()
         if lite_mode:                                          # uvu, no TP weights; mid multiplicity = input multiplicity
             self.linear_scaler = nn.Module()
@@ -888,18 +946,18 @@ class _EmbTP(nn.Module):
         else:
             self.tensor_product = E3TensorProduct(irreps_in, irreps_sh, irreps_out)
             self.linear_scaler = LinearScaleWithWeights(self.tensor_product, Irreps(irreps_out))
-        self.weight_generator = FullyConnectedNet([num_radial] + list(radial_MLP) + [self.linear_scaler.weight_numel])
+        self.weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.linear_scaler.weight_numel], use_kan)
 
 
 class PairInteractionEmbeddingBlock(nn.Module):
-    def __init__(self, num_types, irreps_sh, irreps_out, num_radial, radial_MLP, lite_mode=False):
+    def __init__(self, num_types, irreps_sh, irreps_out, num_radial, radial_MLP, lite_mode=False, use_kan=False):
         super().__init__()
-        self.num_types, self.lite_mode = num_types, lite_mode
+        self.num_types, self.lite_mode, self.use_kan = num_types, lite_mode, bool(use_kan)
         attrs = Irreps([(num_types, 0, 1)])
         self.irreps_sh, self.irreps_out = Irreps(irreps_sh), Irreps(irreps_out)
         self.linear_up_src = E3Linear(attrs, attrs)
         self.linear_up_dst = E3Linear(attrs, attrs)
-        self.conv_tp = _EmbTP(attrs, self.irreps_sh, self.irreps_out, num_radial, radial_MLP, lite_mode)
+        self.conv_tp = _EmbTP(attrs, self.irreps_sh, self.irreps_out, num_radial, radial_MLP, lite_mode, use_kan)
 
     def compile(self, device):
         T = self.num_types
@@ -921,6 +979,7 @@ class PairInteractionEmbeddingBlock(nn.Module):
         delta: the charge-doping correction the forward ran with ([N, num_types]; attrs = one_hot(z) + delta): its gradient is returned
         under the key "_g_delta" (the caller backpropagates it through the charge MLP)."""
         from . import backward_mp as BM
+        _no_kan_backward(self.use_kan, "the backward of the pair embedding")
         dev, T = g_f.device, self.num_types
         if self._wgrad is None:
             sd = getattr(self, "_sd_np", None) or _np_sd(self.conv_tp)
@@ -993,7 +1052,7 @@ class PairInteractionEmbeddingBlock(nn.Module):
             x = ops.embed_lookup(Ts, Td, z, geo.src, geo.dst, geo.E, self.num_types, self._Tp)
         else:
             x = ops.embed_lookup(self._Ts, self._Td, z, geo.src, geo.dst, geo.E, self.num_types, self._Tp)
-        h = ops.radial_hidden_cached(geo, self._h, float(P.ACT_CONSTS[P.ACT_SILU]))
+        h = _hidden_rows(geo, self._h)
         return ops.tp_fused(self._dp, [x], geo.E, h, None, geo, tag="embedding")      # edge features, edge-aligned frame
 
 

@@ -410,6 +410,61 @@ def prefill_radial_hidden(geo: "Geometry", generators: Sequence[Sequence[torch.T
     return True
 
 
+class KanGenerator:
+    """the hidden part of one B-spline KAN weight generator (HamGNN_pre.use_kan) packed for csrc/kan.hip and uploaded: knot tables + W' of every layer but the
+    last (plan.kan_pack_hidden).  `width` = columns of the rows Phi it produces = rows of the W3' the edge programs were built with (plan.kan_last_layer)."""
+
+    def __init__(self, layers, device):
+        blob, self.dims, self.grid_size, self.packed = P.kan_pack_hidden(layers)
+        self.blob = _dev(blob, device, torch.float32)
+        self.h_pad = (self.dims[-1] + 15) // 16 * 16
+        self.width = (self.grid_size + 4) * self.h_pad
+        self.shape_key = (tuple(self.dims), self.grid_size)
+
+
+@_on_tensor_device
+def kan_hidden_multi(rbf: torch.Tensor, generators: Sequence[KanGenerator]) -> torch.Tensor:
+    """Phi [n, E, width] of SEVERAL KAN weight generators of one shape that read the same basis rows, one launch (hg_kan_hidden)"""
+    _require_gpu(rbf)
+    g0 = generators[0]
+    assert all(g.shape_key == g0.shape_key for g in generators), "use_kan: generators of one launch share their layer widths and grid size"
+    assert rbf.dtype == torch.float32 and rbf.is_contiguous() and rbf.shape[1] == g0.dims[0]
+    E = rbf.shape[0]
+    blob = g0.blob if len(generators) == 1 else torch.cat([g.blob for g in generators])
+    out = torch.empty(len(generators), E, g0.width, device=rbf.device, dtype=torch.float32)        # the kernel writes every column, padding included
+    darr = (C.c_int * len(g0.dims))(*g0.dims)
+    check(lib().hg_kan_hidden(ptr(rbf), i64(E), ptr(blob), i64(g0.blob.numel()), i32(len(generators)), darr, i32(len(g0.dims) - 1), i32(g0.grid_size),
+                              i32(1 if g0.packed else 0), ptr(out), _stream()), "hg_kan_hidden")
+    return out
+
+
+def kan_hidden(rbf: torch.Tensor, gen: KanGenerator) -> torch.Tensor:
+    """Phi [E, width] of one KAN weight generator: what the edge kernels take in place of a FullyConnectedNet's hidden rows"""
+    return kan_hidden_multi(rbf, [gen])[0]
+
+
+def kan_hidden_cached(geo: "Geometry", gen: KanGenerator) -> torch.Tensor:
+    """kan_hidden(geo.rbf, gen) through the per-forward cache on the geometry object (radial_hidden_cached's; filled by prefill_kan_hidden)"""
+    cache = geo.__dict__.setdefault("_hcache", {})
+    key = id(gen)
+    if key not in cache:
+        cache[key] = kan_hidden(geo.rbf, gen)
+    return cache[key]
+
+
+def prefill_kan_hidden(geo: "Geometry", generators: Sequence[KanGenerator]) -> bool:
+    """all KAN weight generators of a forward that share a shape in ONE launch each (a backbone: all of them -- 9 for two layers)"""
+    groups: dict = {}
+    for g in generators:
+        groups.setdefault(g.shape_key, []).append(g)
+    cache = geo.__dict__.setdefault("_hcache", {})
+    for gens in groups.values():
+        Phi = kan_hidden_multi(geo.rbf, gens)
+        for m, g in enumerate(gens):
+            cache[id(g)] = Phi[m]
+    return True
+
+
 def mfma_probe(device, iters: int = 4000, reps: int = 3) -> float:
     """fp32 MFMA TFLOP/s the device sustains right now on random operands (hg_mfma_probe: two waves per SIMD on every CU, nothing but
     v_mfma_f32_16x16x4_f32 in the loop) -- the attainable ceiling bench.py quotes beside the nominal peak."""

@@ -22,6 +22,87 @@ def _last_layer(sd, prefix):
     return ks, np.asarray(sd[ks[-1]], dtype=np.float64)
 
 
+# ---- B-spline KAN weight generators (HamGNN_pre.use_kan; reference: toolbox/efficient_kan/kan.py:78-166).  A KANLinear is linear in the expanded row
+# phi(x) = [silu(x_i) | B_0(x_i) .. B_{nb-1}(x_i)]_i, so the generator's LAST layer reaches the edge kernels as an ordinary W3 over the wider "hidden" row
+# Phi = phi(h_last) (csrc/kan.hip): (1 + nb) planes of h_pad channels, plane p of channel c at row p * h_pad + c.
+KAN_SPLINE_ORDER = 3
+KAN_MAX_HIDDEN_LAYERS = 3
+
+
+def is_kan(sd, prefix) -> bool:
+    """the generator `prefix` of a reference-named state dict is a KAN (keys `<prefix>.layers.<i>.base_weight`, ...) rather than an e3nn FullyConnectedNet"""
+    return any(k.startswith(prefix + ".layers.") for k in sd)
+
+
+def kan_layers(sd, prefix):
+    """[(grid [in, G + 7], base_weight [out, in], spline_weight [out, in, G + 3], spline_scaler [out, in])] of a KAN generator, float64, first layer first"""
+    idx = sorted({int(k[len(prefix) + 8:].split(".")[0]) for k in sd if k.startswith(prefix + ".layers.")})
+    assert idx == list(range(len(idx))), idx
+    return [tuple(np.asarray(sd[f"{prefix}.layers.{i}.{n}"], dtype=np.float64) for n in ("grid", "base_weight", "spline_weight", "spline_scaler")) for i in idx]
+
+
+def kan_wprime(base, spline, scaler) -> np.ndarray:
+    """W' [1 + nb, in, out] of one KANLinear: plane 0 = base_weight, plane 1 + j = spline_weight[.., j] * spline_scaler  (y_o = sum_{p, i} phi_p(x_i) W'[p, i, o])"""
+    return np.concatenate([base.T[None], (spline * scaler[..., None]).transpose(2, 1, 0)], 0)
+
+
+def kan_last_layer(sd, prefix):
+    """(W3' [(1 + nb) h_pad, weight_numel] float64, its row count): the last KANLinear of the generator over the rows Phi that csrc/kan.hip writes.  Takes the
+    place of w3 / sqrt(H) in the builders -- a KAN has no 1 / sqrt(fan_in).  Padded channels get ZERO rows (B(0) != 0: the silu(0) = 0 argument of the
+    FullyConnectedNet padding does not hold)."""
+    grid, base, spline, scaler = kan_layers(sd, prefix)[-1]
+    W = kan_wprime(base, spline, scaler)
+    NP, h, n = W.shape
+    hp = ceil_div(h, 16) * 16
+    out = np.zeros((NP, hp, n))
+    out[:, :h] = W
+    return out.reshape(NP * hp, n), NP * hp
+
+
+def _w3_scaled(sd, prefix):
+    """(last radial layer as the builders take it, hidden rows it multiplies): w3 / sqrt(H) of a FullyConnectedNet, W3' of a KAN"""
+    if is_kan(sd, prefix):
+        return kan_last_layer(sd, prefix)
+    _, w3 = _last_layer(sd, prefix)
+    H = w3.shape[0]
+    return w3 / math.sqrt(H), H
+
+
+def kan_knot_table(grid: np.ndarray) -> np.ndarray:
+    """[in, KS] rows  t_0 .. t_{nk-1} | 1 / (t_{j+1} - t_j) | 1 / (t_{j+2} - t_j) | 1 / (t_{j+3} - t_j)  (KS = 4 nk - 6): the knots are read per feature from the
+    state dict (a buffer update_grid may have moved), the Cox-de Boor denominators inverted once here, in fp64"""
+    t = np.asarray(grid, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.concatenate([t] + [1.0 / (t[:, k:] - t[:, :-k]) for k in range(1, KAN_SPLINE_ORDER + 1)], 1)
+
+
+def kan_is_mfma_shape(dims, grid_size) -> bool:
+    """the shape csrc/kan.hip runs on MFMAs (its W' in fragment order): the shipped 64 radial functions -> 64 -> 64 with the reference's grid size 3"""
+    return list(dims) == [64, 64, 64] and int(grid_size) == 3
+
+
+def kan_pack_hidden(layers):
+    """all but the last layer of a KAN generator as csrc/kan.hip reads them: (blob float32, dims [d_0 .. d_last], grid_size, packed)"""
+    hid = layers[:-1]
+    if not 1 <= len(hid) <= KAN_MAX_HIDDEN_LAYERS:
+        raise NotImplementedError(f"use_kan: radial_MLP with {len(hid)} entries (1 to {KAN_MAX_HIDDEN_LAYERS} hidden layers are built)")
+    G = int(layers[0][0].shape[1]) - 2 * KAN_SPLINE_ORDER - 1
+    dims = [int(hid[0][1].shape[1])] + [int(l[1].shape[0]) for l in hid]
+    if any(int(l[0].shape[1]) != G + 7 or int(l[2].shape[2]) != G + 3 for l in layers) or not 1 <= G <= 8:
+        raise NotImplementedError("use_kan: spline order 3 with one grid size from 1 to 8 for all layers of a generator")
+    if max(dims) > 64:
+        raise NotImplementedError("use_kan: radial basis and hidden widths up to 64")
+    packed = kan_is_mfma_shape(dims, G)
+    parts = []
+    for grid, base, spline, scaler in hid:
+        W = kan_wprime(base, spline, scaler)                    # [p, in, out]
+        if packed:                                              # [T][p][rt][lane = (g, i)][q] <- W'[p][16 T + 4 g + q][16 rt + i]
+            W = W.reshape(G + 4, 4, 4, 4, 4, 16).transpose(1, 0, 4, 2, 5, 3)      # [p, T, g, q, rt, i] -> [T, p, rt, g, i, q]
+        parts += [kan_knot_table(grid).reshape(-1), W.reshape(-1)]
+    parts.append(kan_knot_table(layers[-1][0]).reshape(-1))
+    return np.concatenate(parts).astype(np.float32), dims, G, packed
+
+
 @single_thread_blas
 def choose_merge_groups(irreps_node, irreps_edge, irreps_sh, irreps_out, hidden: int, dead_out: Sequence[int] = ()) -> List[List[int]]:
     """Which small output irreps share their MFMA row tiles (add_tp_items merge_groups): per parity class (l + [p odd]) mod 2, the
@@ -95,17 +176,16 @@ def build_message_pack_program(sd: Dict[str, np.ndarray], irreps_node, irreps_ed
     the output rows are written as ZEROS: a caller may use such a program only if it can hand the complete rows to anyone who asks later
     (HamGNNConvE3.declare_consumer keeps the inputs and re-runs the complete program on first access of the public `edge_attr`)."""
     irreps_node, irreps_edge, irreps_sh, irreps_out = Irreps(irreps_node), Irreps(irreps_edge), Irreps(irreps_sh), Irreps(irreps_out)
-    _, w3n = _last_layer(sd, "node_weight_generator")
-    _, w3e = _last_layer(sd, "edge_weight_generator")
-    H = w3n.shape[0]
-    assert H % 4 == 0 and w3e.shape[0] == H
+    w3n, H = _w3_scaled(sd, "node_weight_generator")           # (FullyConnectedNet: w3 / sqrt(H); KAN: W3' over the expanded rows, no 1 / sqrt(H))
+    w3e, He = _w3_scaled(sd, "edge_weight_generator")
+    assert H % 4 == 0 and He == H
     prog, seg_of_k = new_program(irreps_out, H, lambda k, ir: SEG_UNROTATE if unrotate else 0)
     add_tp_items(prog, seg_of_k, PlanarLayout(irreps_node), 2, [SRC_XS, SRC_XD], irreps_sh, irreps_out,
-                 np.asarray(sd["node_tensor_product.weight"]), w3n / math.sqrt(H),
+                 np.asarray(sd["node_tensor_product.weight"]), w3n,
                  np.asarray(sd["node_linear_scaler.linear_out.weight"]), np.asarray(sd["node_linear_out.weight"]), mlp=0,
                  merge_groups=merge_groups, zero_inputs=zero_node, dead_out=dead_out)
     add_tp_items(prog, seg_of_k, PlanarLayout(irreps_edge), 1, [SRC_F], irreps_sh, irreps_out,
-                 np.asarray(sd["edge_tensor_product.weight"]), w3e / math.sqrt(H),
+                 np.asarray(sd["edge_tensor_product.weight"]), w3e,
                  np.asarray(sd["edge_linear_scaler.linear_out.weight"]), np.asarray(sd["edge_linear_out.weight"]), mlp=1,
                  merge_groups=merge_groups, zero_inputs=zero_edge, dead_out=dead_out)
     if skip_weight is not None:
@@ -181,11 +261,10 @@ def build_embedding_program(sd: Dict[str, np.ndarray], num_types, irreps_sh, irr
     """PairInteractionEmbeddingBlock.conv_tp (embeddings.py:328-334, tensor_products.py:170-189): source slot 0 holds
     x = Lin_src(onehot[src]) + Lin_dst(onehot[dst])  (num_types x 0e; identical in every frame)."""
     irreps_sh, irreps_out = Irreps(irreps_sh), Irreps(irreps_out)
-    _, w3 = _last_layer(sd, "weight_generator")
-    H = w3.shape[0]
+    w3, H = _w3_scaled(sd, "weight_generator")
     prog, seg_of_k = new_program(irreps_out, H)
     add_tp_items(prog, seg_of_k, PlanarLayout([(num_types, 0, 1)]), 1, [SRC_XS], irreps_sh, irreps_out,
-                 None if lite_mode else np.asarray(sd["tensor_product.weight"]), w3 / math.sqrt(H),
+                 None if lite_mode else np.asarray(sd["tensor_product.weight"]), w3,
                  np.asarray(sd["linear_scaler.linear_out.weight"]), None, mlp=0, uvu=lite_mode)
     return prog.finalize()
 
@@ -347,13 +426,11 @@ def build_message_pack_program_lite(sd: Dict[str, np.ndarray], irreps_node, irre
     post-op (the pre-combine rows t that the backward's reductions read).  fold: the paths of every (input irrep, output irrep) pair as one
     IT_LINM item (input-stationary kernel; the segment-stationary kernel runs the unfolded IT_LINC items)."""
     irreps_node, irreps_edge, irreps_sh, irreps_out = Irreps(irreps_node), Irreps(irreps_edge), Irreps(irreps_sh), Irreps(irreps_out)
-    _, w3 = _last_layer(sd, "weight_generator_combine")
-    H = w3.shape[0]
+    w3n, H = _w3_scaled(sd, "weight_generator_combine")
     prog, seg_of_k = new_program(irreps_out, H, lambda k, ir: SEG_UNROTATE if unrotate else 0)
     add_lite_branch_items(prog, seg_of_k, PlanarLayout(irreps_node), 2, [SRC_XS, SRC_XD], irreps_sh, irreps_out, np.asarray(sd["node_linear_scaler.weight"]), fold)
     add_lite_branch_items(prog, seg_of_k, PlanarLayout(irreps_edge), 1, [SRC_F], irreps_sh, irreps_out, np.asarray(sd["edge_linear_scaler.weight"]), fold)
     # post-op per segment: scale by the radial weights (one per channel of irreps_out.simplify()) and o3.Linear(out -> out)
-    w3n = w3 / math.sqrt(H)
     lc = np.asarray(sd["combine_messages.linear_out.weight"])
     irs = [(l, p) for _, l, p in irreps_out]
     assert len(set(irs)) == len(irs)
@@ -362,7 +439,7 @@ def build_message_pack_program_lite(sd: Dict[str, np.ndarray], irreps_node, irre
         ch_off[k], lo_off[k] = co, lo
         co += mk
         lo += mk * mk
-    assert co == w3.shape[1] and lo == lc.size
+    assert co == w3n.shape[1] and lo == lc.size
     for k, (mk, lk, pk) in enumerate(irreps_out):
         if not post:
             break

@@ -176,6 +176,8 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
     here and repacked by the next forward (a host-side repack of every block: fine for fine-tuning runs, the thing to make
     incremental for long trainings)."""
     backbone, head = model.representation, model.output_module
+    if getattr(backbone, "use_kan", False):
+        raise NotImplementedError("training_step of a model with HamGNN_pre.use_kan=True is not built (the KAN weight generators run forward only)")
     rep = backbone(batch, save_for_backward=True)
     out = head(batch, rep)
     tgt = target if target is not None else gget(batch, "hamiltonian")

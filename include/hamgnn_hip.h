@@ -58,6 +58,21 @@ int hg_radial_hidden(const float* rbf, int64_t E, const float* weights, const in
  * (grid.y = generator): weights [nmlp][2][64][64] (layer 1 | layer 2, 1/sqrt(fan_in) folded in), h_out [nmlp][E][64].            */
 int hg_radial_hidden_multi(const float* rbf, int64_t E, const float* weights, int nmlp, float act_cst, float* h_out, void* stream);
 
+/* Hidden part of the B-spline KAN weight generators (HamGNN_pre.use_kan; toolbox/efficient_kan/kan.py:78-166, built by
+ * message_passing.py:184-185, tensor_products.py:163-164): for `nmlp` generators of one shape that read the same rows rbf [E][dims[0]],
+ *     h = KANLinear_{nlayers-1}(.. KANLinear_0(rbf)),   phi_out[m][e] = phi(h) = [silu(h_c) | B_0(h_c) .. B_{nb-1}(h_c)]_c
+ * as [nmlp][E][(1 + nb) h_pad] fp32: plane p of channel c at column p * h_pad + c, nb = grid_size + 3 cubic B-spline bases on each
+ * feature's own grid_size + 7 knots, h_pad = dims[nlayers] rounded up to 16, padding channels written as 0.  The generator's last
+ * KANLinear is the linear map phi -> weights that the edge kernels apply as their radial scale.  dims[0..nlayers]: 1..64 each,
+ * nlayers 1..3, grid_size 1..8.  blob: per generator (gen_stride floats apart, == the packed size), for every hidden layer l the
+ * knot table [dims[l]][KS] then W'_l, then the knot table [dims[nlayers]][KS] of the final expansion; a knot table row is
+ * t_0 .. t_{G+6} | 1/(t_{j+1} - t_j) | 1/(t_{j+2} - t_j) | 1/(t_{j+3} - t_j)  (KS = 4 (G + 7) - 6 floats); W'_l = [base_weight |
+ * spline_weight * spline_scaler] as [(1 + nb) dims[l]][dims[l+1]] row-major (row p * dims[l] + i), packed = 0; for the shape
+ * 64 -> 64 -> 64 with grid_size 3 the kernel runs on v_mfma_f32_16x16x4_f32 and W'_l must be in A-fragment order [T][p][rt][lane][4]
+ * (lane (i, g), register q <- W'[p][16 T + 4 g + q][16 rt + i]), packed = 1.  A mismatch of `packed` or `gen_stride` is an error. */
+int hg_kan_hidden(const float* rbf, int64_t E, const float* blob, int64_t gen_stride, int nmlp, const int32_t* dims, int nlayers,
+                  int grid_size, int packed, float* phi_out, void* stream);
+
 /* Measurement aid for bench.py's roofline block (no reference counterpart): nblocks workgroups of 4 waves issue iters x 8
  * v_mfma_f32_16x16x4_f32 each on independent accumulators, operands from in65536 (65 536 floats, caller-filled, e.g. random);
  * out: nblocks * 256 floats (checksum sink).  FLOPs issued = nblocks * 4 * iters * 8 * 2048. */
