@@ -11,6 +11,7 @@ branch `band_energies_soc` (:1998-2286)."""
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional
 
 import numpy as np
@@ -124,9 +125,10 @@ def _crystal_slices(data):
     return out
 
 
-def assemble_k(on, off, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
-    """[nk, M, M] complex64 of one crystal (rows n0:n0+n, edges e0:e0+e) from planar [.., nao^2] blocks"""
-    dev = on.device
+def _pair_tables(data, n0, n, e0, e, orank_all):
+    """the tables hg_hk_assemble and its adjoint share for one crystal (rows n0:n0+n, edges e0:e0+e; integer plumbing): edges grouped by
+    atom pair -> (pair_ptr [npairs + 1], pair_edges [e] crystal-local edge ids, pair_ij [npairs, 2], orank [n, nao], ooff [n] int32, M)"""
+    dev = orank_all.device
     src = (data.edge_index[0][e0:e0 + e] - n0).contiguous()
     dst = (data.edge_index[1][e0:e0 + e] - n0).contiguous()
     key = src * n + dst
@@ -138,9 +140,14 @@ def assemble_k(on, off, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
     orank = orank_all[n0:n0 + n].contiguous()
     norb = (orank >= 0).sum(1)
     ooff = (torch.cumsum(norb, 0) - norb).to(torch.int32).contiguous()
-    M = int(norb.sum())
+    return ptr, order.contiguous(), pij, orank, ooff, int(norb.sum())
+
+
+def assemble_k(on, off, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
+    """[nk, M, M] complex64 of one crystal (rows n0:n0+n, edges e0:e0+e) from planar [.., nao^2] blocks"""
+    ptr, order, pij, orank, ooff, M = _pair_tables(data, n0, n, e0, e, orank_all)
     return ops.hk_assemble(on[n0:n0 + n].contiguous(), off[e0:e0 + e].contiguous(), data.nbr_shift[e0:e0 + e].contiguous().float(),
-                           k_vecs_c.contiguous().float(), ptr, order.contiguous(), pij, n, nao, orank, ooff, M), M
+                           k_vecs_c.contiguous().float(), ptr, order, pij, n, nao, orank, ooff, M), M
 
 
 def _compact_index(orank_all, n0, n):
@@ -154,8 +161,19 @@ def _compact_index(orank_all, n0, n):
 def assemble_k_adjoint(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
     """Adjoint of assemble_k (hg_hk_assemble) for one crystal: G [nk, M, M] complex = the gradient of a real loss with respect to H(k) in
     torch's convention (d/dRe + i d/dIm) -> (g_on [n, nao^2], g_off [e, nao^2]) real.  With H(k)[(i a), (j b)] = on_i[a, b] delta_ij +
-    sum_{e: i -> j} exp(2 pi i k . shift_e) off_e[a, b]:  g_off_e[a, b] = sum_k Re(conj(phase_k(e)) G_k[(i a), (j b)]).  Gathers and
-    one complex multiply-reduce per chunk of k (torch tensor ops; device-agnostic, checked on CPU against autograd)."""
+    sum_{e: i -> j} exp(2 pi i k . shift_e) off_e[a, b]:  g_off_e[a, b] = sum_k Re(conj(phase_k(e)) G_k[(i a), (j b)]).
+    On the GPU: the HIP kernel hg_hk_assemble_adjoint on the pair tables of assemble_k (fixed order, no temporaries).  CPU tensors, and
+    HG_HK_ADJOINT=torch on the GPU, take the torch path below."""
+    if G.is_cuda and os.environ.get("HG_HK_ADJOINT", "").lower() != "torch":
+        ptr, order, pij, orank, ooff, M = _pair_tables(data, n0, n, e0, e, orank_all)
+        return ops.hk_assemble_adjoint(G.to(torch.complex64), data.nbr_shift[e0:e0 + e].contiguous().float(), k_vecs_c.contiguous().float(), ptr, order,
+                                       pij, n, e, nao, orank, ooff, M)
+    return _assemble_k_adjoint_torch(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao)
+
+
+def _assemble_k_adjoint_torch(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
+    """assemble_k_adjoint as gathers and one complex multiply-reduce per chunk of k (torch tensor ops; device-agnostic, any precision,
+    checked on CPU against autograd; [8, e, nao, nao] complex temporaries per chunk)"""
     comp = _compact_index(orank_all, n0, n)                    # [n, nao]
     src = (data.edge_index[0][e0:e0 + e] - n0).long()
     dst = (data.edge_index[1][e0:e0 + e] - n0).long()
@@ -304,10 +322,14 @@ def band_energies_soc(head, real_onsite, imag_onsite, real_offsite, imag_offsite
     return torch.cat(energies, 0), torch.cat(waves, 0)
 
 
-def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, cotangent, k_vecs: Optional[torch.Tensor] = None):
-    """gradient of sum(band_energy * cotangent) with respect to the real-space blocks (the band-energy loss of the reference's second
-    training stage, Model.py:150-196 with prediction: band_energy): H(k) from the assembly kernel, the Cholesky / eigh chain
-    differentiated by torch.autograd (library solvers, as in the forward), then the assembly's adjoint.  Returns (g_on, g_off)."""
+def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, cotangent, k_vecs: Optional[torch.Tensor] = None, gap_cotangent=None):
+    """gradient of sum(band_energy * cotangent) + sum(band_gap * gap_cotangent) with respect to the real-space blocks (the band_energy /
+    band_gap losses of the reference's second training stage, Model.py:150-196): H(k) from the assembly kernel, the Cholesky / eigh chain
+    differentiated by torch.autograd (library solvers, as in the forward) ONCE per crystal for both terms, then the assembly's adjoint
+    (hg_hk_assemble_adjoint).  cotangent [sum_c bands_c, num_k] or None, gap_cotangent [n_crystals] or None.  The gap is a min / max over k
+    of the two bands around half filling, taken before the band window is cut (_eig_chain).  Returns (g_on, g_off)."""
+    if cotangent is None and gap_cotangent is None:
+        raise ValueError("band_energy_backward: neither a band-energy nor a band-gap cotangent")
     nao = head.nao_max
     dev = onsite_hamiltonian.device
     k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs).to(dev)
@@ -323,9 +345,15 @@ def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, co
         Sk, _ = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
         with torch.enable_grad():
             Hk = Hk.detach().requires_grad_()
-            evals = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])[0].transpose(-1, -2)     # [bands, nk]
+            evals, _, _, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+            evals = evals.transpose(-1, -2)                    # [bands, nk]
             nb = evals.shape[0]
-            (G,) = torch.autograd.grad((evals * cotangent[row:row + nb].to(evals.dtype)).sum(), Hk)
+            scalar = 0.0
+            if cotangent is not None:
+                scalar = scalar + (evals * cotangent[row:row + nb].to(evals.dtype)).sum()
+            if gap_cotangent is not None:
+                scalar = scalar + (gap * gap_cotangent[c].to(gap.dtype)).sum()
+            (G,) = torch.autograd.grad(scalar, Hk)
         row += nb
         a, b = assemble_k_adjoint(G, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
         g_on[n0:n0 + n] = a

@@ -290,7 +290,7 @@ class HamGNNPlusPlusOut(nn.Module):
         return on, off
 
     # ---- backward of the read-out (K6 data gradient + the head's weight gradients): non-SOC and SOC / so3
-    def backward(self, data, graph_representation, grad_hamiltonian, grad_unshifted=None):
+    def backward(self, data, graph_representation, grad_hamiltonian, grad_unshifted=None, grad_overlap=None):
         """grad_hamiltonian: gradient with respect to result["hamiltonian"] in the forward's row order -- non-SOC: [N + E, nao^2];
         SOC / so3: [2 (N + E), (2 nao)^2] = [real rows; imaginary rows].  Returns (g_node_planar [N, Dp], g_edge_planar_rot [E, Dp] --
         gradients of the representation's planar node rows and edge-frame edge rows --, {parameter name: gradient}).
@@ -300,9 +300,15 @@ class HamGNNPlusPlusOut(nn.Module):
         SOC / so3 (hamgnn_output.py:3026-3144; csrc/head.hip soc_assemble_kernel): the (2 nao)^2 gradient rows are folded back onto the
         spin-free block (uu + dd of the real part) and onto ksi (the three L components x the antihermitised blocks), the shell-block
         mean is its own adjoint (hg_block_mean), then the ksi networks' HamLayer.backward.  With add_H_nonsoc the spin-free block is an
-        input (the non-SOC model's prediction) and only the ksi path carries gradients -- the Uni-HamGNN SOC training mode."""
-        if not self.ham_only:
-            raise NotImplementedError("head backward: ham_only=True (reference overlaps)")
+        input (the non-SOC model's prediction) and only the ksi path carries gradients -- the Uni-HamGNN SOC training mode.
+        ham_only=False (hamgnn_output.py:2995-3019, 4009-4013): grad_overlap is the gradient with respect to result["overlap"], [N + E, nao^2]
+        in the forward's per-crystal row order.  The overlap blocks are spin-free read-outs of the same node / edge-frame rows under every
+        head type (no H0): their backward is the spin-free chain above on the two overlap networks, its g_node / g_edge are added to the
+        Hamiltonian path's, the parameter gradients come back under {onsite,offsite}_overlap_network.*.  grad_overlap=None: those
+        parameters get zeros and the overlap path runs no kernels.  The zero-point shift's adjoint and grad_unshifted act on the
+        Hamiltonian rows only."""
+        if grad_overlap is not None and self.ham_only:
+            raise ValueError("head backward: grad_overlap given, but ham_only=True built no overlap networks")
         rep = graph_representation
         ops.require_fp32(self, data)                           # `precision: 64` raises instead of returning fp32-accurate rows
         dev = data.z.device
@@ -317,6 +323,22 @@ class HamGNNPlusPlusOut(nn.Module):
             gH = self._zero_point_shift_adjoint(data, gH, edge_counts)
         if grad_unshifted is not None:                         # gradient with respect to the blocks BEFORE the shift (the band energies read those)
             gH = gH + grad_unshifted.float()
+        g_node, g_edge, grads = self._backward_hamiltonian(data, geo, node_pl, edge_rot, inv, edge_counts, gH)
+        if self.ham_only:
+            return g_node, g_edge, grads
+        nets = ("onsite_overlap_network", "offsite_overlap_network")
+        if grad_overlap is None:                               # no loss on the overlap: its networks are not evaluated (their parameters get zeros)
+            for name in nets:
+                grads.update({f"{name}.{k}": torch.zeros_like(p).reshape(-1) for k, p in getattr(self, name).named_parameters()})
+            return g_node, g_edge, grads
+        gS_on, gS_off = (t.contiguous() for t in self._split_by_crystal(data, grad_overlap.float(), edge_counts))
+        gn, ge, gw = self._backward_spin_free(data, geo, node_pl, edge_rot, inv, gS_on, gS_off, nets=nets)
+        grads.update(gw)
+        return g_node + gn, g_edge + ge, grads
+
+    def _backward_hamiltonian(self, data, geo, node_pl, edge_rot, inv, edge_counts, gH):
+        """the Hamiltonian networks' part of backward(): gH = the gradient of the rows before the zero-point shift"""
+        n = self.nao_max
         g_node = g_edge = None
         grads = {}
         if self.soc_switch and self.soc_basis == "su2":
@@ -370,24 +392,26 @@ class HamGNNPlusPlusOut(nn.Module):
             g_a = 0.5 * (g_a - other.transpose(1, 2))
         return (g_a * L.reshape(-1, n, n, 3)).sum(-1).reshape(-1, n * n), g_h
 
-    def _backward_spin_free(self, data, geo, node_pl, edge_rot, inv, gH_on, gH_off):
+    def _backward_spin_free(self, data, geo, node_pl, edge_rot, inv, gH_on, gH_off, nets=("onsite_hamiltonian_network", "offsite_hamiltonian_network")):
         z = data.z.contiguous()
         n = self.nao_max
         # mask . symmetrise is self-adjoint (the orbital mask of an edge equals the transposed mask of its inverse edge)
         g_on = ops.ham_finish(gH_on, None, None, self._mask, z, None, None, n, 1.0, self.symmetrize)
         g_off = ops.ham_finish(gH_off, inv, None, self._mask, z, geo.src, geo.dst, n, 1.0, self.symmetrize)
-        return self._backward_merge("so3", (self._slot,) + self._cg, geo, node_pl, edge_rot, g_on, g_off)
+        return self._backward_merge("so3", (self._slot,) + self._cg, geo, node_pl, edge_rot, g_on, g_off, nets=nets)
 
-    def _backward_merge(self, key, tables, geo, node_pl, edge_rot, g_on, g_off):
+    def _backward_merge(self, key, tables, geo, node_pl, edge_rot, g_on, g_off, nets=("onsite_hamiltonian_network", "offsite_hamiltonian_network")):
         """adjoint of the CG merge + reorder (a CSR map applied transposed: hg_ham_merge with plan.ham_merge_adjoint_tables), of the
-        off-site un-rotation (hg_rotate_gather) and of the two Hamiltonian HamLayers"""
+        off-site un-rotation (hg_rotate_gather) and of the two HamLayers `nets` (the Hamiltonian networks, or the overlap networks: both
+        read the so3 tables, which compile() builds from whichever network the head has with the spin-free ham irreps)"""
+        net_on, net_off = getattr(self, nets[0]), getattr(self, nets[1])
         dev = g_on.device
         # structural tables (CG merge maps: functions of the basis, not of the weights): built once per (key, table object) -- rebuilding them
         # after every optimiser step put a device -> host copy in the middle of the step
         cache = self.__dict__.setdefault("_adj_tabs_by", {})
         key = (key, str(tables[0].device))                     # (per device: an id()-keyed entry outlives its tables and could be recycled)
         if key not in cache:
-            glay = P.PlanarLayout(self.onsite_hamiltonian_network.girr)
+            glay = P.PlanarLayout(net_on.girr)
             st, ptr_, idx_, val_ = (t.cpu().numpy() for t in tables)
             sid, pT, iT, vT, scat = P.ham_merge_adjoint_tables(st, ptr_, idx_, val_, glay.dim)
             cache[key] = tuple(torch.from_numpy(a).to(dev) for a in (sid, pT, iT, vT, scat)) + (
@@ -395,10 +419,10 @@ class HamGNNPlusPlusOut(nn.Module):
         sid, pT, iT, vT, scat, rot_g, ncoef = cache[key]
         gc_on = ops.from_planar(ops.ham_merge(g_on, None, sid, pT, iT, vT, ncoef), scat)
         gc_off = ops.rotate_gather(ops.from_planar(ops.ham_merge(g_off, None, sid, pT, iT, vT, ncoef), scat), None, geo, rot_g)
-        g_node, gw_on = self.onsite_hamiltonian_network.backward(node_pl, gc_on)
-        g_edge, gw_off = self.offsite_hamiltonian_network.backward(edge_rot, gc_off)
-        grads = {"onsite_hamiltonian_network." + k: v for k, v in gw_on.items()}
-        grads.update({"offsite_hamiltonian_network." + k: v for k, v in gw_off.items()})
+        g_node, gw_on = net_on.backward(node_pl, gc_on)
+        g_edge, gw_off = net_off.backward(edge_rot, gc_off)
+        grads = {nets[0] + "." + k: v for k, v in gw_on.items()}
+        grads.update({nets[1] + "." + k: v for k, v in gw_off.items()})
         return g_node, g_edge, grads
 
     def edge_irreps_read(self):

@@ -888,6 +888,25 @@ def hk_assemble(on, off, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_atoms
 
 
 @_on_tensor_device
+def hk_assemble_adjoint(G, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_atoms, n_edges, nao, orank, ooff, M):
+    """(g_on [n_atoms, nao^2], g_off [n_edges, nao^2]) from the gradient G [nk, M, M] complex64 with respect to H(k) of one crystal: the
+    adjoint of hk_assemble on the same pair tables (see include/hamgnn_hip.h:hg_hk_assemble_adjoint); every output element is written"""
+    _require_gpu(G)
+    nk = int(kvec.shape[0])
+    if G.dtype != torch.complex64 or tuple(G.shape) != (nk, M, M):
+        raise ValueError(f"hk_assemble_adjoint: G must be complex64 [{nk}, {M}, {M}], got {G.dtype} {tuple(G.shape)}")
+    if nk <= 0 or M <= 0 or n_atoms <= 0:                      # (the entry point launches nothing then)
+        return (torch.zeros(n_atoms, nao * nao, device=G.device, dtype=torch.float32), torch.zeros(n_edges, nao * nao, device=G.device, dtype=torch.float32))
+    Gr = torch.view_as_real(G.contiguous())
+    g_on = torch.empty(n_atoms, nao * nao, device=G.device, dtype=torch.float32)
+    g_off = torch.empty(n_edges, nao * nao, device=G.device, dtype=torch.float32)
+    check(lib().hg_hk_assemble_adjoint(ptr(Gr), ptr(nbr_shift), ptr(kvec), i32(nk), ptr(pair_ptr), ptr(pair_edges), ptr(pair_ij), i64(pair_ij.shape[0]),
+                                       i32(n_atoms), i64(n_edges), i32(nao), ptr(orank.to(torch.int32).contiguous()), ptr(ooff), i32(M), ptr(g_on),
+                                       ptr(g_off), _stream()), "hg_hk_assemble_adjoint")
+    return g_on, g_off
+
+
+@_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""
     _require_gpu(H)

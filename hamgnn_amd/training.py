@@ -4,8 +4,12 @@ hamgnn/models/Model.py:150-196), on the HIP kernels and without an autograd grap
   training_step(model, batch, ...)   forward with the layer inputs kept -> loss(es) -> head backward -> backbone backward -> `.grad` of EVERY
                                      parameter in the reference's names / flat layouts (any torch optimiser steps them); both backbones
                                      (HamGNNConvE3, HamGNNTransformer), the non-SOC / SOC so3 / SOC su2 heads, `losses=[{metric, prediction:
-                                     hamiltonian | hamiltonian_real | hamiltonian_imag | band_energy, target, loss_weight}]` as in the reference's config; hamiltonian-type
-                                     losses are multiplied by the head's `sparsity_ratio` as the reference does (Model.py:158-162)
+                                     hamiltonian | hamiltonian_real | hamiltonian_imag | band_energy | band_gap | overlap, target, loss_weight}]` as in
+                                     the reference's config (metric: mae | mse | rmse | cosine_similarity | euclidean_loss | sum_zero,
+                                     hamgnn/utils/losses.py); hamiltonian-type losses are multiplied by the head's `sparsity_ratio` as the reference
+                                     does (Model.py:158-162), `overlap` (a ham_only=False head) and the k-space losses are not; `band_energy` and
+                                     `band_gap` of one step share one eigen-chain per crystal (kspace.band_energy_backward).  `wavefunction` and
+                                     `peak` are not built: the reference's own config names a metric for them that its parser lacks, and no head emits `peak`
   head_training_step(...)            the cheap variant for a frozen backbone (its representation can be reused across steps)
   allreduce_gradients(model)         data-parallel training (the reference's DDP): mean of the ranks' gradients, one flat bucket
   parallel.shard_graph(g, r, w)      model-parallel training of ONE large crystal: pass the rank's shard to training_step -- node-level partial
@@ -25,9 +29,31 @@ from .topo import gget
 
 
 def _loss_and_grad(pred: torch.Tensor, target: torch.Tensor, metric: str):
+    """(loss, d loss / d pred) of the reference's metrics (hamgnn/utils/losses.py; parse_metric_func): mae | mse | rmse element-wise, and the
+    three row-wise ones with the reference's axes -- cosine_similarity = mean(1 - <p, t> / (|p| |t|)) and euclidean_loss = mean |p - t|_2 with
+    the products / norms over the LAST axis and the mean over all others (a 1-D prediction is one row); sum_zero = |sum over axis 0 of p|_2
+    over the last axis (the target is not read; a 1-D prediction gives |sum p|; beyond 2-D the reference's expression is not a scalar)"""
+    metric = metric.lower()
+    if metric in ("cosine_similarity", "euclidean_loss", "sum_zero"):
+        if metric == "sum_zero":
+            if pred.dim() > 2:
+                raise ValueError("sum_zero: the reference's expression is a scalar for 1-D and 2-D predictions only")
+            p2 = pred.reshape(pred.shape[0], -1) if pred.dim() else pred.reshape(1, 1)
+            v = p2.sum(0)
+            nv = torch.linalg.vector_norm(v)
+            return nv, (v / nv.clamp_min(1e-30)).expand_as(p2).reshape(pred.shape)
+        p2 = pred.reshape(-1, pred.shape[-1]) if pred.dim() else pred.reshape(1, 1)
+        t2 = target.reshape(p2.shape)
+        rows = p2.shape[0]
+        if metric == "euclidean_loss":
+            d = p2 - t2
+            nd = torch.linalg.vector_norm(d, dim=1, keepdim=True)
+            return nd.mean(), (d / (rows * nd.clamp_min(1e-30))).reshape(pred.shape)
+        npd, ntg = torch.linalg.vector_norm(p2, dim=1, keepdim=True), torch.linalg.vector_norm(t2, dim=1, keepdim=True)
+        cos = (p2 * t2).sum(1, keepdim=True) / (npd * ntg)
+        return (1.0 - cos).mean(), (-(t2 / (npd * ntg) - cos * p2 / (npd * npd)) / rows).reshape(pred.shape)
     diff = pred - target
     n = diff.numel()
-    metric = metric.lower()
     if metric == "mae":
         return diff.abs().mean(), torch.sign(diff) / n
     if metric == "mse":
@@ -35,7 +61,7 @@ def _loss_and_grad(pred: torch.Tensor, target: torch.Tensor, metric: str):
     if metric == "rmse":
         rm = torch.sqrt((diff * diff).mean())
         return rm, diff / (n * rm.clamp_min(1e-30))
-    raise ValueError(f"unsupported loss metric {metric!r} (mae | mse | rmse)")
+    raise ValueError(f"unsupported loss metric {metric!r} (mae | mse | rmse | cosine_similarity | euclidean_loss | sum_zero)")
 
 
 def _loss_and_grad_sharded(pred, target, metric: str, n_on: int):
@@ -171,8 +197,9 @@ def enable_row_programs(module):
 @torch.no_grad()
 def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tensor] = None, losses=None) -> Dict[str, torch.Tensor]:
     """One loss / gradient evaluation of the WHOLE model (HamGNNConvE3 backbone + non-SOC HamGNNPlusPlusOut head): forward with the
-    layer inputs kept, loss(hamiltonian, target), backward through head and backbone on the GPU kernels, `.grad` of every parameter set
-    (accumulated if already present).  The caller owns the optimiser (`opt.step(); opt.zero_grad()`); all packed weights are dropped
+    layer inputs kept, loss(hamiltonian, target) or the `losses` list (module docstring), backward through head and backbone on the GPU
+    kernels, `.grad` of every parameter set (accumulated if already present; the overlap networks of a ham_only=False head get zeros
+    unless a loss names `overlap`).  The caller owns the optimiser (`opt.step(); opt.zero_grad()`); all packed weights are dropped
     here and repacked by the next forward (a host-side repack of every block: fine for fine-tuning runs, the thing to make
     incremental for long trainings)."""
     backbone, head = model.representation, model.output_module
@@ -184,6 +211,7 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
     if tgt is None:
         raise ValueError("training_step: the batch carries no target (Hon / Hoff or hamiltonian)")
     H = out["hamiltonian"]
+    g_overlap = None                                           # gradient w.r.t. result["overlap"] (losses with prediction: overlap)
     sharded = parallel.is_sharded(batch)
     if sharded:
         # model-parallel step on an edge-sharded crystal: the on-site rows are replicated, every rank holds its own off-site rows
@@ -196,10 +224,11 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
     elif losses is None:
         loss, gH = _sparsity_weighted(out, *_loss_and_grad(H, tgt.to(H.dtype), metric))
     else:
-        # the reference's `losses` list (Model.py:150-196): [{metric, prediction, target, loss_weight}] over `hamiltonian` and / or
-        # `band_energy` (the second training stage: bands of H(k) against the bands of the target Hamiltonian)
+        # the reference's `losses` list (Model.py:150-196): [{metric, prediction, target, loss_weight}] over the Hamiltonian rows, the overlap
+        # rows and / or `band_energy` / `band_gap` (the second training stage: bands of H(k) against the bands of the target Hamiltonian)
         loss, gH = H.new_zeros(()), torch.zeros_like(H)
-        g_unshifted = None                                     # gradient w.r.t. the blocks before the zero-point shift (band energies)
+        g_unshifted = None                                     # gradient w.r.t. the blocks before the zero-point shift (band energies, band gap)
+        g_bands = g_gap = None                                 # cotangents of the k-space losses: ONE band_energy_backward call after the loop
         for spec in losses:
             w, pred = float(spec.get("loss_weight", 1.0)), spec["prediction"].lower()
             if pred == "hamiltonian":
@@ -216,34 +245,54 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
                 li, gi = _sparsity_weighted(out, *_loss_and_grad(H[rows], t_.to(H.dtype), spec["metric"]))
                 gH[rows] += w * gi
             elif pred == "band_energy":
-                from . import kspace
                 if out.get("band_energy") is None:
                     raise ValueError("a band_energy loss needs HamGNNPlusPlusOut(calculate_band_energy=True)")
                 be = out["band_energy"]
                 li, gbe = _loss_and_grad(be, gget(batch, spec.get("target", "band_energy").lower()).to(be.dtype), spec["metric"])
-                edge_counts = head._global_inverse(batch)[1]
-                Hb = H
                 if head.zero_point_shift:
                     # the bands were computed from the blocks BEFORE the shift (hamgnn_output.py:3802-3880 precede :3971-3981) and then aligned
-                    # by their mean (:3983-3985): the forward kept the unshifted rows for this re-evaluation; adjoint of the alignment = g - mean(g)
+                    # by their mean (:3983-3985): adjoint of the alignment = g - mean(g)
                     gbe = gbe - gbe.mean()
-                    Hb = head._unshifted
-                if getattr(head, "soc_switch", False):
-                    # spin-orbit head: rows [real (N + E); imaginary (N + E)] of width (2 nao)^2, the bands of the stacked spinor H(k)
-                    half = Hb.shape[0] // 2
-                    on_r, off_r = head._split_by_crystal(batch, Hb[:half], edge_counts)
-                    on_i, off_i = head._split_by_crystal(batch, Hb[half:], edge_counts)
-                    gs = kspace.band_energy_backward_soc(head, on_r.contiguous(), on_i.contiguous(), off_r.contiguous(), off_i.contiguous(), batch, w * gbe)
-                    gb = torch.cat([head._cat_by_crystal(batch, gs[0], gs[2], edge_counts), head._cat_by_crystal(batch, gs[1], gs[3], edge_counts)], 0)
-                else:
-                    on, off = head._split_by_crystal(batch, Hb, edge_counts)
-                    g_on, g_off = kspace.band_energy_backward(head, on.contiguous(), off.contiguous(), batch, w * gbe)
-                    gb = head._cat_by_crystal(batch, g_on, g_off, edge_counts)
-                g_unshifted = gb if g_unshifted is None else g_unshifted + gb
+                g_bands = w * gbe if g_bands is None else g_bands + w * gbe
+            elif pred == "band_gap":
+                # the gap of the bands around half filling (hamgnn_output.py:1930-1936): non-SOC head only, as in the reference; computed from
+                # the unshifted blocks, and the mean alignment of the bands under zero_point_shift does not touch it
+                if out.get("band_gap") is None:
+                    raise ValueError("a band_gap loss needs a non-SOC HamGNNPlusPlusOut(calculate_band_energy=True): the spin-orbit heads emit no band_gap")
+                gp = out["band_gap"]
+                li, ggp = _loss_and_grad(gp, gget(batch, spec.get("target", "band_gap").lower()).to(gp.dtype), spec["metric"])
+                g_gap = w * ggp if g_gap is None else g_gap + w * ggp
+            elif pred == "overlap":
+                # the overlap networks' prediction (ham_only=False) against the reference overlaps; no sparsity_ratio factor (Model.py:158-162
+                # applies it to the three hamiltonian predictions only)
+                if getattr(head, "ham_only", True) or out.get("overlap") is None:
+                    raise ValueError("an overlap loss needs HamGNNPlusPlusOut(ham_only=False): ham_only=True builds no overlap networks")
+                Sp = out["overlap"]
+                t_ = gget(batch, spec.get("target", "overlap").lower())
+                if t_ is None:
+                    t_ = head._cat_by_crystal(batch, gget(batch, "Son"), gget(batch, "Soff"), head._global_inverse(batch)[1])
+                li, gi = _loss_and_grad(Sp, t_.to(Sp.dtype), spec["metric"])
+                g_overlap = w * gi if g_overlap is None else g_overlap + w * gi
             else:
-                raise ValueError(f"training_step: losses on {pred!r} are not built (hamiltonian | hamiltonian_real | hamiltonian_imag | band_energy)")
+                raise ValueError(f"training_step: losses on {pred!r} are not built (hamiltonian | hamiltonian_real | hamiltonian_imag | band_energy | band_gap | overlap)")
             loss = loss + w * li
-    g_node, g_edge, g_head = head.backward(batch, rep, gH, grad_unshifted=g_unshifted if losses is not None and not sharded else None)
+        if g_bands is not None or g_gap is not None:
+            from . import kspace
+            edge_counts = head._global_inverse(batch)[1]
+            Hb = head._unshifted if head.zero_point_shift else H  # (the forward kept the unshifted rows for this re-evaluation)
+            if getattr(head, "soc_switch", False):
+                # spin-orbit head: rows [real (N + E); imaginary (N + E)] of width (2 nao)^2, the bands of the stacked spinor H(k)
+                half = Hb.shape[0] // 2
+                on_r, off_r = head._split_by_crystal(batch, Hb[:half], edge_counts)
+                on_i, off_i = head._split_by_crystal(batch, Hb[half:], edge_counts)
+                gs = kspace.band_energy_backward_soc(head, on_r.contiguous(), on_i.contiguous(), off_r.contiguous(), off_i.contiguous(), batch, g_bands)
+                g_unshifted = torch.cat([head._cat_by_crystal(batch, gs[0], gs[2], edge_counts), head._cat_by_crystal(batch, gs[1], gs[3], edge_counts)], 0)
+            else:
+                on, off = head._split_by_crystal(batch, Hb, edge_counts)
+                g_on, g_off = kspace.band_energy_backward(head, on.contiguous(), off.contiguous(), batch, g_bands, gap_cotangent=g_gap)
+                g_unshifted = head._cat_by_crystal(batch, g_on, g_off, edge_counts)
+    okw = {} if g_overlap is None else {"grad_overlap": g_overlap}
+    g_node, g_edge, g_head = head.backward(batch, rep, gH, grad_unshifted=g_unshifted if losses is not None and not sharded else None, **okw)
     g_back = backbone.backward(batch, rep, g_node, g_edge)
     if sharded:                                                # per-edge parameters: sum the ranks' partial gradients (one flat bucket each)
         parallel.allreduce_edge_summed_gradients(g_head, batch)

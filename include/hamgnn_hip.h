@@ -330,6 +330,21 @@ int hg_hk_assemble(const float* on, const float* off, const float* nbr_shift, co
                    const int64_t* pair_edges, const int64_t* pair_ij, int64_t npairs, int n_atoms, int nao, const int32_t* orank,
                    const int32_t* ooff, int M, float* Hk, void* stream);
 
+/* Adjoint of hg_hk_assemble for ONE crystal (the k-space losses of the training step: band_energy, band_gap), same pair tables.
+ * G [nk][M][M] complex64 (re, im): gradient of a real loss with respect to X(k) in the convention d/dRe + i d/dIm.
+ *   g_on[i][a, b]  = sum_k Re G_k[(i a), (i b)]
+ *   g_off[e][a, b] = sum_k Re(conj(phase_k(e)) G_k[(i a), (j b)])   for edge e: i -> j,  phase_k(e) = exp(2 pi i k . nbr_shift_e)
+ * Elements whose orbital a or b the atom lacks (orank < 0) are written as 0: EVERY element of g_on [n_atoms][nao^2] and g_off
+ * [n_edges][nao^2] is written (every edge belongs to one pair), the caller zero-fills nothing.  Edges of a self-image pair (i, i) read the
+ * diagonal block g_on[i] reads.  The phase is computed in double (|k . shift| reaches tens of turns), once per (edge, k) and workgroup; one
+ * workgroup owns one atom pair, one thread one element, k ascending: fixed summation order, no atomics, two launches are bit-identical.
+ * n_atoms <= 0, nk <= 0 or M <= 0: returns 0 without a launch; npairs == 0: g_on is still written.  Refused (-2): nao^2 > 1024 and
+ * npairs > 2^31 - 1 (the layout's limits: pairs on grid.x, a thread owns up to four block elements), and nk > 65535 (not a grid
+ * limit here: k is looped; it is the most hg_hk_assemble can have produced G for).                                                      */
+int hg_hk_assemble_adjoint(const float* G, const float* nbr_shift, const float* kvec, int nk, const int64_t* pair_ptr,
+                           const int64_t* pair_edges, const int64_t* pair_ij, int64_t npairs, int n_atoms, int64_t n_edges, int nao,
+                           const int32_t* orank, const int32_t* ooff, int M, float* g_on, float* g_off, void* stream);
+
 /* e3nn o3.Linear on planar rows as one streaming pass (every o3.Linear of the hot path: hamgnn/nn/interaction_blocks.py:332-358,
  * 141-152; nn/convolution.py:127; models/hamgnn_output.py:49-58).  Tables from hamgnn_amd/plan.py:linear_tables:
  * items int32[nitems][2] = {unit, component a}: the wave units of one block of 32 rows (one workgroup per four of them),
