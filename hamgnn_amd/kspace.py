@@ -194,24 +194,123 @@ def _assemble_k_adjoint_torch(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
     return g_on, (g_off * ok).reshape(e, nao * nao)
 
 
-def _eig_chain(head, Hk, Sk, val_c, z_c):
-    """generalized eigenproblem through the Cholesky factor of S(k), as the reference (:1911-1928) -> (evals, evecs, Ht, gap)"""
+def _eig_solve(Hk, Sk):
+    """generalized eigenproblem through the Cholesky factor of S(k), as the reference (:1911-1928) -> (evals [k, M], evecs [k, band, M], Ht)"""
     L = torch.linalg.cholesky(Sk)
     Linv = torch.linalg.inv(L)
     LHinv = torch.linalg.inv(L.conj().transpose(-1, -2))
     Ht = torch.bmm(torch.bmm(Linv, Hk), LHinv)
     evals, evecs = torch.linalg.eigh(Ht)
     evecs = torch.einsum("ijk,ika->iaj", LHinv, evecs)
+    return evals, evecs, Ht
+
+
+def _window_bounds(head, val_c, z_c):
+    """(half, lo, hi): the band below which half the valence electrons sit, and the band window [lo:hi] of band_num_control (None, None: all bands)"""
     half = math.ceil(float(val_c.sum()) / 2)
-    gap = (evals[:, half].min() - evals[:, half - 1].max()).reshape(1)
     bnc = head.band_num_control
-    if bnc is not None:
-        if isinstance(bnc, dict):
-            nb = int(sum(int(bnc.get(int(zz), bnc.get(str(int(zz)), 0))) for zz in z_c.tolist()))
-            evals, evecs = evals[:, :nb], evecs[:, :nb, :]
-        else:
-            win = max(1, int(bnc * half)) if isinstance(bnc, float) else min(int(bnc), half)
-            evals, evecs = evals[:, half - win:half + win], evecs[:, half - win:half + win, :]
+    if bnc is None:
+        return half, None, None
+    if isinstance(bnc, dict):
+        return half, 0, int(sum(int(bnc.get(int(zz), bnc.get(str(int(zz)), 0))) for zz in z_c.tolist()))
+    win = max(1, int(bnc * half)) if isinstance(bnc, float) else min(int(bnc), half)
+    return half, half - win, half + win
+
+
+def _gap_and_window(head, evals, evecs, val_c, z_c):
+    """the band gap (min / max over ALL k of the two bands around half filling, before the window is cut) and the band window -> (evals, evecs, gap)"""
+    half, lo, hi = _window_bounds(head, val_c, z_c)
+    gap = (evals[:, half].min() - evals[:, half - 1].max()).reshape(1)
+    if lo is not None:
+        evals, evecs = evals[:, lo:hi], evecs[:, lo:hi, :]
+    return evals, evecs, gap
+
+
+def _eig_chain(head, Hk, Sk, val_c, z_c):
+    """_eig_solve on all k-points of a crystal + gap + band window -> (evals, evecs, Ht, gap)"""
+    evals, evecs, Ht = _eig_solve(Hk, Sk)
+    evals, evecs, gap = _gap_and_window(head, evals, evecs, val_c, z_c)
+    return evals, evecs, Ht, gap
+
+
+# ------------------------------------------------------------------------------------------------ edge-sharded crystal (parallel.shard_graph)
+# Every rank holds all atoms and its own edges.  H(k) and S(k) are sums over edges: each rank assembles its partial matrices for ALL k (the replicated
+# on-site rows enter on rank 0 only), one all-reduce makes them whole, and the k-points are dealt to the ranks in contiguous blocks for the Cholesky /
+# eigh chain -- the dominant cost of the step.  Eigenvalues (and, in the forward, eigenvectors) are all-gathered, so everything derived from all k (band
+# window, gap) is computed identically on every rank.  The backward gathers the per-block gradient G of H(k) and runs the assembly's adjoint over the
+# rank's own edges with all k: the on-site gradient comes out identical on every rank, the off-site gradient is the rank's own.
+def _shard_of(data):
+    """(rank, world) of an edge-sharded graph, else None"""
+    from . import parallel
+    if not parallel.is_sharded(data):
+        return None
+    import torch.distributed as dist
+    if not dist.is_initialized():
+        raise RuntimeError("graph is sharded but torch.distributed is not initialised")
+    return tuple(int(v) for v in data.get("_hg_shard"))
+
+
+def _single_crystal(data):
+    sl = _crystal_slices(data)
+    if len(sl) != 1:
+        raise ValueError("the k-space step on an edge-sharded graph: a sharded graph holds exactly one crystal")
+    return sl
+
+
+def _own_onsite(on, shard):
+    """the replicated on-site rows enter the summed assembly once: on rank 0"""
+    return on if shard is None or shard[0] == 0 else torch.zeros_like(on)
+
+
+def _k_block(shard, nk):
+    """[k0, k1): the contiguous block of k-points this rank solves (empty when nk < world for some ranks)"""
+    rank, world = shard
+    return rank * nk // world, (rank + 1) * nk // world
+
+
+def _sum_over_ranks(mat):
+    """sum of the ranks' partial [nk, M, M] complex matrices (as real pairs: gloo takes no complex tensors)"""
+    import torch.distributed as dist
+    buf = torch.view_as_real(mat.contiguous()).contiguous()
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    return torch.view_as_complex(buf)
+
+
+def _gather_k(block, shard, nk):
+    """the ranks' k-blocks [k1 - k0, ...] (real or complex) -> [nk, ...] in k order on every rank; blocks are padded to the largest one"""
+    import torch.distributed as dist
+    world = shard[1]
+    sizes = [(r + 1) * nk // world - r * nk // world for r in range(world)]
+    cplx = block.is_complex()
+    b = torch.view_as_real(block.contiguous()) if cplx else block
+    buf = b.new_zeros((max(sizes),) + tuple(b.shape[1:]))
+    buf[:b.shape[0]] = b
+    parts = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(parts, buf)
+    out = torch.cat([p[:sz] for p, sz in zip(parts, sizes)], 0).contiguous()
+    return torch.view_as_complex(out) if cplx else out
+
+
+def broadcast_k_vectors(k_vecs, data):
+    """random (or path) k-vectors of a sharded graph: rank 0's, on every rank"""
+    if _shard_of(data) is None:
+        return k_vecs
+    import torch.distributed as dist
+    k_vecs = k_vecs.contiguous()
+    dist.broadcast(k_vecs, src=0)
+    return k_vecs
+
+
+def _eig_chain_sharded(head, Hk, Sk, val_c, z_c, shard):
+    """_eig_chain on the summed H(k), S(k) of a sharded crystal: this rank solves its k-block, the blocks are gathered"""
+    nk, M = int(Hk.shape[0]), int(Hk.shape[1])
+    k0, k1 = _k_block(shard, nk)
+    if k1 > k0:
+        evals, evecs, Ht = _eig_solve(Hk[k0:k1], Sk[k0:k1])
+    else:
+        evals, evecs, Ht = Hk.real.new_zeros(0, M), Hk.new_zeros(0, M, M), Hk.new_zeros(0, M, M)
+    evals, evecs, Ht = (_gather_k(t, shard, nk) for t in (evals, evecs, Ht))
+    evals, evecs, gap = _gap_and_window(head, evals, evecs, val_c, z_c)
     return evals, evecs, Ht, gap
 
 
@@ -229,10 +328,14 @@ def band_energies(head, onsite_hamiltonian, offsite_hamiltonian, data, k_vecs: O
     val = head._num_valence.to(dev)[z].to(torch.float64)
     energies, waves, gaps, hsyms = [], [], [], []
     Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data)):
-        Hk, M = assemble_k(onsite_hamiltonian, offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sk, _ = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        evals, evecs, Ht, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+    shard = _shard_of(data)
+    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
+        Hk, M = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        Sk, _ = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        if shard is None:
+            evals, evecs, Ht, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+        else:
+            evals, evecs, Ht, gap = _eig_chain_sharded(head, _sum_over_ranks(Hk), _sum_over_ranks(Sk), val[n0:n0 + n], z[n0:n0 + n], shard)
         gaps.append(gap)
         energies.append(evals.transpose(-1, -2))
         waves.append(evecs.reshape(-1))
@@ -247,6 +350,9 @@ def band_energies_export(head, onsite_hamiltonian, offsite_hamiltonian, data, ov
     HK [C, num_k, M, M], SK [C, num_k, M, M] (the reference overlap, or the predicted one), dSK [C, num_k, M, M, 3] from data.dSon / dSoff,
     band_gap [C]).  As in the reference the eigenproblem is always solved with the REFERENCE overlap (:1603), and the per-crystal results are
     stacked, i.e. every crystal of the batch must have the same number of orbitals."""
+    if _shard_of(data) is not None:
+        raise NotImplementedError("export_reciprocal_values on an edge-sharded graph is not built: H(k), S(k) and dS(k) would be those of the rank's "
+                                  "own edges only; run the export on the whole crystal")
     nao = head.nao_max
     dev = onsite_hamiltonian.device
     k_vecs = gget(data, "k_vecs") if k_vecs is None else k_vecs
@@ -279,6 +385,36 @@ def band_energies_export(head, onsite_hamiltonian, offsite_hamiltonian, data, ov
     return torch.cat(energies, 0), torch.stack(waves, 0), torch.stack(HKs, 0), torch.stack(SKs, 0), torch.stack(dSKs, 0), torch.cat(gaps, 0)
 
 
+def _soc_overlap(Sk, Hk, M):
+    """kron(1_2, S(k)) (:2165-2167) in the shape of the spinor H(k)"""
+    Ssoc = torch.zeros_like(Hk)
+    Ssoc[:, :M, :M] = Sk
+    Ssoc[:, M:, M:] = Sk
+    return Ssoc
+
+
+def _soc_solve(Hk, Ssoc, vectors=True):
+    """the spinor eigenproblem through the Cholesky factor of kron(1_2, S(k)) (:2236-2252) -> (evals [k, 2 M], evecs [k, 2 M, band] or None)"""
+    L = torch.linalg.cholesky(Ssoc)
+    Linv = torch.linalg.inv(L)
+    LHinv = torch.linalg.inv(L.conj().transpose(-1, -2))
+    if not vectors:
+        return torch.linalg.eigvalsh(torch.bmm(torch.bmm(Linv, Hk), LHinv)), None
+    evals, evecs = torch.linalg.eigh(torch.bmm(torch.bmm(Linv, Hk), LHinv))
+    return evals, torch.bmm(LHinv, evecs)
+
+
+def _soc_window_bounds(head, val_c, z_c):
+    """the band window [lo:hi] of band_num_control on a spin-orbit head (:2254-2263), or (None, None): all bands"""
+    bnc = head.band_num_control
+    if bnc is None:
+        return None, None
+    if isinstance(bnc, dict):
+        return 0, int(sum(int(bnc.get(int(zz), bnc.get(str(int(zz)), 0))) for zz in z_c.tolist()))
+    nval = int(val_c.sum())
+    return nval - int(bnc), nval + int(bnc)
+
+
 def band_energies_soc(head, real_onsite, imag_onsite, real_offsite, imag_offsite, data, k_vecs: Optional[torch.Tensor] = None):
     """calculate_band_energies_with_spin_orbit_coupling of the reference (hamgnn_output.py:1998-2286): spinor Hamiltonian rows
     [., (2 nao)^2] (real and imaginary part, on-site and off-site) -> (band_energy [sum_c bands_c, num_k], wavefunction (flattened)).
@@ -286,7 +422,8 @@ def band_energies_soc(head, real_onsite, imag_onsite, real_offsite, imag_offsite
     real part + i x assembly of its imaginary part (the assembly is linear), eight launches of hg_hk_assemble -- stacked to [2 M, 2 M];
     S(k) is the spin-free overlap on both spin diagonals (kron(1_2, S(k)), :2165-2167); generalised eigenproblem through the Cholesky
     factor of S(k) (:2236-2252, hipSOLVER through torch.linalg); band window :2254-2263 (dict: leading bands; int: +- that many bands
-    around the number of valence electrons)."""
+    around the number of valence electrons).  Edge-sharded crystal: the stacked H(k) and S(k) are summed over the ranks once each, every rank
+    solves its block of k-points, eigenvalues and eigenvectors are gathered (see _eig_chain_sharded)."""
     nao = head.nao_max
     dev = real_onsite.device
     k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs)
@@ -298,28 +435,53 @@ def band_energies_soc(head, real_onsite, imag_onsite, real_offsite, imag_offsite
     val = head._num_valence.to(dev)[z].to(torch.float64)
     Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
     energies, waves = [], []
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data)):
-        Sk, M = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Hk = _soc_hk(real_onsite, imag_onsite, real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e, orank_all, nao)   # [nk, 2 M, 2 M]
-        Ssoc = torch.zeros_like(Hk)
-        Ssoc[:, :M, :M] = Sk
-        Ssoc[:, M:, M:] = Sk
-        L = torch.linalg.cholesky(Ssoc)
-        Linv = torch.linalg.inv(L)
-        LHinv = torch.linalg.inv(L.conj().transpose(-1, -2))
-        evals, evecs = torch.linalg.eigh(torch.bmm(torch.bmm(Linv, Hk), LHinv))
-        evecs = torch.bmm(LHinv, evecs)
-        bnc = head.band_num_control
-        if bnc is not None:
-            if isinstance(bnc, dict):
-                nb = int(sum(int(bnc.get(int(zz), bnc.get(str(int(zz)), 0))) for zz in z[n0:n0 + n].tolist()))
-                evals, evecs = evals[:, :nb], evecs[:, :nb, :]
+    shard = _shard_of(data)
+    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
+        Sk, M = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e,
+                     orank_all, nao)                           # [nk, 2 M, 2 M]
+        if shard is None:
+            evals, evecs = _soc_solve(Hk, _soc_overlap(Sk, Hk, M))
+        else:
+            Hk, Sk = _sum_over_ranks(Hk), _sum_over_ranks(Sk)
+            nk = int(Hk.shape[0])
+            k0, k1 = _k_block(shard, nk)
+            if k1 > k0:
+                evals, evecs = _soc_solve(Hk[k0:k1], _soc_overlap(Sk[k0:k1], Hk[k0:k1], M))
             else:
-                nval = int(val[n0:n0 + n].sum())
-                evals, evecs = evals[:, nval - int(bnc):nval + int(bnc)], evecs[:, nval - int(bnc):nval + int(bnc), :]
+                evals, evecs = Hk.real.new_zeros(0, 2 * M), Hk.new_zeros(0, 2 * M, 2 * M)
+            evals, evecs = _gather_k(evals, shard, nk), _gather_k(evecs, shard, nk)
+        lo, hi = _soc_window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
+        if lo is not None:
+            evals, evecs = evals[:, lo:hi], evecs[:, lo:hi, :]
         energies.append(evals.transpose(-1, -2))
         waves.append(evecs.reshape(-1))
     return torch.cat(energies, 0), torch.cat(waves, 0)
+
+
+def _sharded_chain_gradient(solve, Hk, shard, cot_window, lo, hi, gap=None):
+    """G [nk, M, M] = gradient of sum(window(evals) * cot_window) (+ gap term) with respect to the summed H(k) of a sharded crystal: the cotangent is
+    laid out on the eigenvalues of ALL bands and k [nk, bands]; this rank differentiates `solve` (H(k) block -> evals) on its k-block with its slice
+    of the cotangent, and the blocks of G are gathered.  gap: (half, cotangent scalar) -- the gap is min_k evals[:, half] - max_k evals[:, half - 1], so
+    its cotangent is one-hot at the arg-min / arg-max of the GATHERED eigenvalues and joins the band cotangent: one chain per k-point."""
+    nk, nb_all = int(Hk.shape[0]), int(Hk.shape[1])
+    k0, k1 = _k_block(shard, nk)
+    with torch.enable_grad():
+        Hb = Hk[k0:k1].detach().requires_grad_()
+        evals = solve(Hb, k0, k1) if k1 > k0 else Hk.real.new_zeros(0, nb_all)
+        C = torch.zeros(nk, nb_all, device=Hk.device, dtype=evals.dtype)
+        if cot_window is not None:
+            C[:, lo:hi] = cot_window.to(evals.dtype).transpose(0, 1)
+        if gap is not None:
+            half, gc = gap
+            full = _gather_k(evals.detach(), shard, nk)
+            C[torch.argmin(full[:, half]), half] += gc.to(evals.dtype)
+            C[torch.argmax(full[:, half - 1]), half - 1] -= gc.to(evals.dtype)
+        if k1 > k0:
+            (Gb,) = torch.autograd.grad((evals * C[k0:k1]).sum(), Hb)
+        else:
+            Gb = torch.zeros_like(Hb)
+    return _gather_k(Gb.detach(), shard, nk)
 
 
 def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, cotangent, k_vecs: Optional[torch.Tensor] = None, gap_cotangent=None):
@@ -327,7 +489,9 @@ def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, co
     band_gap losses of the reference's second training stage, Model.py:150-196): H(k) from the assembly kernel, the Cholesky / eigh chain
     differentiated by torch.autograd (library solvers, as in the forward) ONCE per crystal for both terms, then the assembly's adjoint
     (hg_hk_assemble_adjoint).  cotangent [sum_c bands_c, num_k] or None, gap_cotangent [n_crystals] or None.  The gap is a min / max over k
-    of the two bands around half filling, taken before the band window is cut (_eig_chain).  Returns (g_on, g_off)."""
+    of the two bands around half filling, taken before the band window is cut (_eig_chain).  Returns (g_on, g_off).
+    Edge-sharded crystal: H(k), S(k) summed over the ranks, the chain differentiated on this rank's k-block, G gathered, the adjoint over the
+    rank's own edges with all k -- g_on is the whole crystal's on every rank, g_off belongs to the rank's edges (_sharded_chain_gradient)."""
     if cotangent is None and gap_cotangent is None:
         raise ValueError("band_energy_backward: neither a band-energy nor a band-gap cotangent")
     nao = head.nao_max
@@ -340,20 +504,29 @@ def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, co
     g_on = torch.zeros_like(onsite_hamiltonian)
     g_off = torch.zeros_like(offsite_hamiltonian)
     row = 0
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data)):
-        Hk, M = assemble_k(onsite_hamiltonian, offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sk, _ = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        with torch.enable_grad():
-            Hk = Hk.detach().requires_grad_()
-            evals, _, _, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
-            evals = evals.transpose(-1, -2)                    # [bands, nk]
-            nb = evals.shape[0]
-            scalar = 0.0
-            if cotangent is not None:
-                scalar = scalar + (evals * cotangent[row:row + nb].to(evals.dtype)).sum()
-            if gap_cotangent is not None:
-                scalar = scalar + (gap * gap_cotangent[c].to(gap.dtype)).sum()
-            (G,) = torch.autograd.grad(scalar, Hk)
+    shard = _shard_of(data)
+    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
+        Hk, M = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        Sk, _ = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        if shard is None:
+            with torch.enable_grad():
+                Hk = Hk.detach().requires_grad_()
+                evals, _, _, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+                evals = evals.transpose(-1, -2)                    # [bands, nk]
+                nb = evals.shape[0]
+                scalar = 0.0
+                if cotangent is not None:
+                    scalar = scalar + (evals * cotangent[row:row + nb].to(evals.dtype)).sum()
+                if gap_cotangent is not None:
+                    scalar = scalar + (gap * gap_cotangent[c].to(gap.dtype)).sum()
+                (G,) = torch.autograd.grad(scalar, Hk)
+        else:
+            Hk, Sk = _sum_over_ranks(Hk), _sum_over_ranks(Sk)
+            half, lo, hi = _window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
+            nb = len(range(M)[slice(lo, hi)])
+            G = _sharded_chain_gradient(lambda Hb, k0, k1: _eig_solve(Hb, Sk[k0:k1])[0], Hk, shard,
+                                        None if cotangent is None else cotangent[row:row + nb], lo, hi,
+                                        gap=None if gap_cotangent is None else (half, gap_cotangent[c]))
         row += nb
         a, b = assemble_k_adjoint(G, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
         g_on[n0:n0 + n] = a
@@ -380,7 +553,8 @@ def band_energy_backward_soc(head, real_onsite, imag_onsite, real_offsite, imag_
     spin-orbit head; Model.py:150-196 with prediction: band_energy, bands from hamgnn_output.py:1998-2286).  As band_energy_backward: the
     Cholesky / eigh chain on the stacked [2 M, 2 M] H(k) is differentiated by torch.autograd (library solvers), then every spin block of
     the gradient G goes through the assembly's adjoint -- G_ab for the real rows, -i G_ab for the imaginary rows (H_ab = A(real) + i A(imag)
-    with the real-linear assembly A).  Returns (g_real_on, g_imag_on, g_real_off, g_imag_off) in the rows' [., 2, nao, 2, nao] layout."""
+    with the real-linear assembly A).  Returns (g_real_on, g_imag_on, g_real_off, g_imag_off) in the rows' [., 2, nao, 2, nao] layout.
+    Edge-sharded crystal: as band_energy_backward (the on-site gradients are the whole crystal's on every rank)."""
     nao = head.nao_max
     dev = real_onsite.device
     k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs).to(dev)
@@ -390,29 +564,27 @@ def band_energy_backward_soc(head, real_onsite, imag_onsite, real_offsite, imag_
     Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
     g = [torch.zeros(t.shape[0], 2, nao, 2, nao, device=dev, dtype=torch.float32) for t in (real_onsite, imag_onsite, real_offsite, imag_offsite)]
     row = 0
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data)):
-        Sk, M = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Hk = _soc_hk(real_onsite, imag_onsite, real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Ssoc = torch.zeros_like(Hk)
-        Ssoc[:, :M, :M] = Sk
-        Ssoc[:, M:, M:] = Sk
-        with torch.enable_grad():
-            Hk = Hk.detach().requires_grad_()
-            L = torch.linalg.cholesky(Ssoc)
-            Linv = torch.linalg.inv(L)
-            LHinv = torch.linalg.inv(L.conj().transpose(-1, -2))
-            evals = torch.linalg.eigvalsh(torch.bmm(torch.bmm(Linv, Hk), LHinv))
-            bnc = head.band_num_control
-            if bnc is not None:
-                if isinstance(bnc, dict):
-                    nb = int(sum(int(bnc.get(int(zz), bnc.get(str(int(zz)), 0))) for zz in z[n0:n0 + n].tolist()))
-                    evals = evals[:, :nb]
-                else:
-                    nval = int(val[n0:n0 + n].sum())
-                    evals = evals[:, nval - int(bnc):nval + int(bnc)]
-            evals = evals.transpose(-1, -2)                    # [bands, nk]
-            nb = evals.shape[0]
-            (G,) = torch.autograd.grad((evals * cotangent[row:row + nb].to(evals.dtype)).sum(), Hk)
+    shard = _shard_of(data)
+    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
+        Sk, M = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e,
+                     orank_all, nao)
+        lo, hi = _soc_window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
+        if shard is None:
+            Ssoc = _soc_overlap(Sk, Hk, M)
+            with torch.enable_grad():
+                Hk = Hk.detach().requires_grad_()
+                evals, _ = _soc_solve(Hk, Ssoc, vectors=False)
+                if lo is not None:
+                    evals = evals[:, lo:hi]
+                evals = evals.transpose(-1, -2)                    # [bands, nk]
+                nb = evals.shape[0]
+                (G,) = torch.autograd.grad((evals * cotangent[row:row + nb].to(evals.dtype)).sum(), Hk)
+        else:
+            Hk, Sk = _sum_over_ranks(Hk), _sum_over_ranks(Sk)
+            nb = len(range(2 * M)[slice(lo, hi)])
+            G = _sharded_chain_gradient(lambda Hb, k0, k1: _soc_solve(Hb, _soc_overlap(Sk[k0:k1], Hb, M), vectors=False)[0], Hk, shard,
+                                        cotangent[row:row + nb], lo, hi)
         row += nb
         for a in (0, 1):
             for b in (0, 1):

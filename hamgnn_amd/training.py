@@ -13,7 +13,9 @@ hamgnn/models/Model.py:150-196), on the HIP kernels and without an autograd grap
   head_training_step(...)            the cheap variant for a frozen backbone (its representation can be reused across steps)
   allreduce_gradients(model)         data-parallel training (the reference's DDP): mean of the ranks' gradients, one flat bucket
   parallel.shard_graph(g, r, w)      model-parallel training of ONE large crystal: pass the rank's shard to training_step -- node-level partial
-                                     sums are all-reduced inside the backward, per-edge parameter gradients summed over the ranks
+                                     sums are all-reduced inside the backward, per-edge parameter gradients summed over the ranks; the `losses` list
+                                     works on a shard too (row losses: on-site rows once + the ranks' off-site rows; band_energy / band_gap: H(k) and
+                                     S(k) summed over the ranks, the k-points dealt to them -- kspace.py)
   weights_changed(model)             after `optimizer.step()`: message blocks repack their weights on the device at the next forward
                                      (hamgnn_amd/repack.py); training_step calls it for the step that follows
 
@@ -65,8 +67,8 @@ def _loss_and_grad(pred: torch.Tensor, target: torch.Tensor, metric: str):
 
 
 def _loss_and_grad_sharded(pred, target, metric: str, n_on: int):
-    """loss over [replicated on-site rows; this rank's off-site rows] of an edge-sharded crystal == the loss of the whole crystal:
-    the off-site sums are added up over the ranks, the on-site rows counted once"""
+    """the element-wise metrics (mae | mse | rmse) over [replicated on-site rows; this rank's off-site rows] of an edge-sharded crystal == the
+    loss of the whole crystal: the off-site sums are added up over the ranks, the on-site rows counted once"""
     import torch.distributed as dist
     diff = pred - target
     metric = metric.lower()
@@ -83,6 +85,42 @@ def _loss_and_grad_sharded(pred, target, metric: str, n_on: int):
         return total.to(pred.dtype), 2.0 * diff / n
     rm = torch.sqrt(total)
     return rm.to(pred.dtype), diff / (n * rm.clamp_min(1e-30).to(pred.dtype))
+
+
+def _row_loss_and_grad_sharded(pred, target, metric: str, n_on: int):
+    """every metric of _loss_and_grad on the rows of an edge-sharded crystal, i.e. _loss_and_grad on [on-site rows once; all ranks' off-site
+    rows] (the formulas of hamgnn/utils/losses.py): the element-wise metrics through _loss_and_grad_sharded; the row-wise ones reduce their
+    per-row statistics in one small all-reduce -- the sum of the off-site rows' 1 - cos or |p - t|_2 and the row count; sum_zero the column
+    sums of the off-site rows."""
+    import torch.distributed as dist
+    metric = metric.lower()
+    if metric not in ("cosine_similarity", "euclidean_loss", "sum_zero"):
+        if metric not in ("mae", "mse", "rmse"):
+            raise ValueError(f"unsupported loss metric {metric!r} (mae | mse | rmse | cosine_similarity | euclidean_loss | sum_zero)")
+        return _loss_and_grad_sharded(pred, target, metric, n_on)
+    if pred.dim() != 2:
+        raise ValueError(f"{metric} on an edge-sharded graph: [rows, columns] predictions (the Hamiltonian / overlap rows)")
+    if metric == "sum_zero":
+        part = pred[n_on:].sum(0).double()
+        dist.all_reduce(part, op=dist.ReduceOp.SUM)
+        v = (part + pred[:n_on].sum(0).double()).to(pred.dtype)
+        nv = torch.linalg.vector_norm(v)
+        return nv, (v / nv.clamp_min(1e-30)).expand_as(pred)
+    t2 = target.reshape(pred.shape)
+    if metric == "euclidean_loss":
+        d = pred - t2
+        per_row = torch.linalg.vector_norm(d, dim=1, keepdim=True)
+    else:
+        npd, ntg = torch.linalg.vector_norm(pred, dim=1, keepdim=True), torch.linalg.vector_norm(t2, dim=1, keepdim=True)
+        cos = (pred * t2).sum(1, keepdim=True) / (npd * ntg)
+        per_row = 1.0 - cos
+    stats = torch.stack([per_row[n_on:].sum().double(), torch.tensor(float(pred.shape[0] - n_on), dtype=torch.float64, device=pred.device)])
+    dist.all_reduce(stats, op=dist.ReduceOp.SUM)
+    rows = float(stats[1]) + n_on
+    total = ((stats[0] + per_row[:n_on].sum().double()) / rows).to(pred.dtype)
+    if metric == "euclidean_loss":
+        return total, d / (rows * per_row.clamp_min(1e-30))
+    return total, -(t2 / (npd * ntg) - cos * pred / (npd * npd)) / rows
 
 
 def _sparsity_weighted(out, loss, grad):
@@ -212,28 +250,32 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
         raise ValueError("training_step: the batch carries no target (Hon / Hoff or hamiltonian)")
     H = out["hamiltonian"]
     g_overlap = None                                           # gradient w.r.t. result["overlap"] (losses with prediction: overlap)
+    g_unshifted = None                                         # gradient w.r.t. the blocks before the zero-point shift (band energies, band gap)
     sharded = parallel.is_sharded(batch)
     if sharded:
-        # model-parallel step on an edge-sharded crystal: the on-site rows are replicated, every rank holds its own off-site rows
-        if losses is not None:
-            raise NotImplementedError("training_step on an edge-sharded graph: the plain hamiltonian loss")
-        loss, gH = _loss_and_grad_sharded(H, tgt.to(H.dtype), metric, int(batch.z.shape[0]))
-        if out.get("sparsity_ratio") is not None:              # the ratio of the WHOLE crystal (the shard's own count would differ per rank)
-            sr = _sharded_sparsity_ratio(head, batch).to(loss.dtype)
-            loss, gH = loss * sr, gH * sr
-    elif losses is None:
-        loss, gH = _sparsity_weighted(out, *_loss_and_grad(H, tgt.to(H.dtype), metric))
+        # model-parallel step on an edge-sharded crystal: the on-site rows are replicated, every rank holds its own off-site rows.  The row-wise
+        # losses count the on-site rows once and sum the off-site rows over the ranks; the sparsity ratio is the WHOLE crystal's (the shard's own
+        # count would differ per rank)
+        n_on = int(batch.z.shape[0])
+        row_loss = lambda p_, t_, m_: _row_loss_and_grad_sharded(p_, t_, m_, n_on)
+        sr = _sharded_sparsity_ratio(head, batch) if out.get("sparsity_ratio") is not None else None
+        ham_weighted = lambda l_, g_: (l_, g_) if sr is None else (l_ * sr.to(l_.dtype), g_ * sr.to(l_.dtype))
+    else:
+        row_loss = _loss_and_grad
+        ham_weighted = lambda l_, g_: _sparsity_weighted(out, l_, g_)
+    if losses is None:
+        loss, gH = ham_weighted(*row_loss(H, tgt.to(H.dtype), metric))
     else:
         # the reference's `losses` list (Model.py:150-196): [{metric, prediction, target, loss_weight}] over the Hamiltonian rows, the overlap
-        # rows and / or `band_energy` / `band_gap` (the second training stage: bands of H(k) against the bands of the target Hamiltonian)
+        # rows and / or `band_energy` / `band_gap` (the second training stage: bands of H(k) against the bands of the target Hamiltonian).
+        # On an edge-sharded crystal the bands and the gap in `out` are the whole crystal's on every rank (kspace.py): their losses are plain
         loss, gH = H.new_zeros(()), torch.zeros_like(H)
-        g_unshifted = None                                     # gradient w.r.t. the blocks before the zero-point shift (band energies, band gap)
         g_bands = g_gap = None                                 # cotangents of the k-space losses: ONE band_energy_backward call after the loop
         for spec in losses:
             w, pred = float(spec.get("loss_weight", 1.0)), spec["prediction"].lower()
             if pred == "hamiltonian":
                 t_ = gget(batch, spec["target"].lower()) if spec.get("target") else tgt
-                li, gi = _sparsity_weighted(out, *_loss_and_grad(H, t_.to(H.dtype), spec["metric"]))
+                li, gi = ham_weighted(*row_loss(H, t_.to(H.dtype), spec["metric"]))
                 gH += w * gi
             elif pred in ("hamiltonian_real", "hamiltonian_imag"):
                 # SOC heads: result["hamiltonian"] = [real rows; imaginary rows] (hamgnn_output.py:3621-3626 attaches the targets alike)
@@ -242,7 +284,7 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
                 half = H.shape[0] // 2
                 rows = slice(0, half) if pred == "hamiltonian_real" else slice(half, None)
                 t_ = gget(batch, spec.get("target", pred).lower())
-                li, gi = _sparsity_weighted(out, *_loss_and_grad(H[rows], t_.to(H.dtype), spec["metric"]))
+                li, gi = ham_weighted(*row_loss(H[rows], t_.to(H.dtype), spec["metric"]))
                 gH[rows] += w * gi
             elif pred == "band_energy":
                 if out.get("band_energy") is None:
@@ -271,7 +313,7 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
                 t_ = gget(batch, spec.get("target", "overlap").lower())
                 if t_ is None:
                     t_ = head._cat_by_crystal(batch, gget(batch, "Son"), gget(batch, "Soff"), head._global_inverse(batch)[1])
-                li, gi = _loss_and_grad(Sp, t_.to(Sp.dtype), spec["metric"])
+                li, gi = row_loss(Sp, t_.to(Sp.dtype), spec["metric"])
                 g_overlap = w * gi if g_overlap is None else g_overlap + w * gi
             else:
                 raise ValueError(f"training_step: losses on {pred!r} are not built (hamiltonian | hamiltonian_real | hamiltonian_imag | band_energy | band_gap | overlap)")
@@ -292,7 +334,7 @@ def training_step(model, batch, metric: str = "mae", target: Optional[torch.Tens
                 g_on, g_off = kspace.band_energy_backward(head, on.contiguous(), off.contiguous(), batch, g_bands, gap_cotangent=g_gap)
                 g_unshifted = head._cat_by_crystal(batch, g_on, g_off, edge_counts)
     okw = {} if g_overlap is None else {"grad_overlap": g_overlap}
-    g_node, g_edge, g_head = head.backward(batch, rep, gH, grad_unshifted=g_unshifted if losses is not None and not sharded else None, **okw)
+    g_node, g_edge, g_head = head.backward(batch, rep, gH, grad_unshifted=g_unshifted, **okw)
     g_back = backbone.backward(batch, rep, g_node, g_edge)
     if sharded:                                                # per-edge parameters: sum the ranks' partial gradients (one flat bucket each)
         parallel.allreduce_edge_summed_gradients(g_head, batch)
