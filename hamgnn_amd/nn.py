@@ -13,7 +13,7 @@ from __future__ import annotations
 import os
 
 import math
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -265,10 +265,31 @@ class _CombineMessages(nn.Module):
 MP_KERNEL_DEFAULT = "auto"
 
 
+def _mp_kernel() -> str:
+    """HG_MP_KERNEL = seg | is | auto: which schedule of the fused edge programs runs (default: see DESIGN.md section 5)"""
+    return os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT)
+
+
+def _upload_adjoint(prog, device):
+    """a data-gradient program on the device: input-stationary, over several workgroups per tile if need be, unless HG_MP_KERNEL=seg"""
+    try:
+        return ops.DeviceProgram(prog, device, schedule="is_parts" if _mp_kernel() != "seg" else "seg")
+    except NotImplementedError:                                # tiles / staging do not fit even split over workgroups: segment-stationary kernel
+        return ops.DeviceProgram(prog, device, schedule="seg")
+
+
 def _wgrad_runner(wg, dpA, dpB):
     """backward_mp's run_program on the device: the two materialisation programs on the segment-stationary fused kernel"""
     dps = {id(wg.progA): dpA, id(wg.progB): dpB}
     return lambda prog, srcs, hn, he: ops.tp_fused(dps[id(prog)], [t.contiguous() for t in srcs], srcs[0].shape[0], hn, he, None, tag="wgrad_rows")
+
+
+class _Uploaded(NamedTuple):
+    """one uploaded program of a MessagePackBlock"""
+    dev: object            # ops.DeviceProgram / ops.DeviceWgFused; None: no kernel instantiation takes it (not tried again)
+    tag: tuple             # names its packer: everything that changes the STRUCTURE of the weight blob
+    build: Callable        # (state dict, skip weight) -> host program / tables: what was uploaded, and what refresh() probes (repack.AffinePack)
+    uses_skip: bool        # the blob holds the fused skip o3.Linear
 
 
 class MessagePackBlock(nn.Module):
@@ -279,6 +300,7 @@ class MessagePackBlock(nn.Module):
         self.use_kan = bool(use_kan)
         self.irreps_node, self.irreps_edge = Irreps(irreps_node_feats), Irreps(irreps_edge_feats)
         self.irreps_sh, self.irreps_out = Irreps(irreps_local_env_edge), Irreps(irreps_out)
+        self._irreps = (self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out)
         comb = Irreps([(max(1, 2 * m), l, p) for m, l, p in self.irreps_node])
         if lite_mode:                                          # message_passing.py:99-111, 123-125 (uvu products carry no weights)
             self.node_linear_scaler = _MidLinear(comb, self.irreps_sh, self.irreps_out)
@@ -294,7 +316,36 @@ class MessagePackBlock(nn.Module):
             self.edge_weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.edge_linear_scaler.weight_numel], self.use_kan)
             self.node_linear_out = E3Linear(self.irreps_out, self.irreps_out)
             self.edge_linear_out = E3Linear(self.irreps_out, self.irreps_out)
-        self._dp = None
+        self._zeros, self._dead = ((), ()), ()                 # set_structural_zeros / set_dead_outputs: read by the next compile()
+        # structural (depend on the irreps only), survive recompiles: the packers by tag, the L' block-GEMM units, the rotate table of the output rows
+        self._packers, self._bg_lp, self._rt_out = {}, None, None
+        self._wg = self._wg_prev = None                        # backward_mp.MessagePackWeightGrad of the compiled weights (built on first use), and the one before
+        self._reset(None, False, None, None)
+
+    def _reset(self, device, unrotate, skip_weight, skip_source):
+        """ALL state of one compile(), reset here and nowhere else: nothing uploaded yet"""
+        self._device, self._unrotate = device, bool(unrotate)
+        # the fused skip o3.Linear: its weight as compile() got it, and (a tuple: not registered as a sub-module) the module that holds the weight of the moment
+        self._skip_weight, self._skip_source = skip_weight, skip_source
+        self._zkw_compiled = {}                                # what the reduced programs of THIS compile assume (everybody plans with it, not with the environment of the moment)
+        self._dp = None                                        # the complete forward program as compiled: self._programs[("forward", False, False)].dev
+        self._programs = {}                                    # ("forward", reduced, plain) | ("adjoint", reduced) | ("wgrad rows", "A" / "B") | ("wgrad fused", reduced)
+        self._groups = self._groups_z = ()                     # merge groups of the complete / the reduced forward program; empty: compiled plain, no twins for split launches
+        self._hn = self._he = None
+        self._adj_maps = None
+        self._lite_bw = None
+        self._wg_prev, self._wg = (self._wg or self._wg_prev), None     # the device constants of the weight gradients are handed over (adopt_constants)
+
+    def programs(self) -> Dict[tuple, object]:
+        """read-only: {key: device object} of what this block holds on the device now (keys as in _reset)"""
+        return {k: e.dev for k, e in self._programs.items() if e.dev is not None}
+
+    # the names these had before the table, for readers outside the class (checks and benchmark scripts written against them): read-only views of it
+    _dp_adj = property(lambda self: self.programs().get(("adjoint", False)))
+    _dp_adj_z = property(lambda self: self.programs().get(("adjoint", True)))
+    _wgrad_fused = property(lambda self: self.programs().get(("wgrad fused", False)))
+    _wgrad_fused_z = property(lambda self: self.programs().get(("wgrad fused", True)))
+    _wgrad = property(lambda self: self._wg and [self._wg, self.programs().get(("wgrad rows", "A")), self.programs().get(("wgrad rows", "B"))])
 
     def set_structural_zeros(self, node=(), edge=()):
         """irreps (indices into irreps_node / irreps_edge) whose rows are STRUCTURALLY zero where this block runs (the first layer: node rows out of an
@@ -311,163 +362,137 @@ class MessagePackBlock(nn.Module):
         return self
 
     def _zero_kw(self):
-        """what the REDUCED forward program of this block may assume (plan.build_message_pack_program): structurally zero input irreps, unread output irreps"""
-        zn, ze = getattr(self, "_zeros", ((), ()))
-        dead = getattr(self, "_dead", ())
+        """what the REDUCED forward program of this block may assume (plan.build_message_pack_program): structurally zero input irreps, unread output irreps.
+        HG_STRUCT_ZEROS / HG_DEAD_OUT are compile-time switches: read here, by compile(), and recorded in _zkw_compiled"""
+        zn, ze = self._zeros
         if self.lite_mode:
             return {}
         kw = {}
         if os.environ.get("HG_STRUCT_ZEROS", "1") != "0" and (zn or ze):
             kw.update(zero_node=zn, zero_edge=ze)
-        if os.environ.get("HG_DEAD_OUT", "1") != "0" and dead:
-            kw["dead_out"] = dead
+        if os.environ.get("HG_DEAD_OUT", "1") != "0" and self._dead:
+            kw["dead_out"] = self._dead
         return kw
 
     def _zero_inputs_kw(self):
         """the structurally zero INPUT irreps alone (what the backward programs may assume: paths that read zeros have zero weight gradients, and nobody
-        reads the gradient of a structurally zero input)"""
-        return {k: v for k, v in self._zero_kw().items() if k in ("zero_node", "zero_edge")}
+        reads the gradient of a structurally zero input), as compiled"""
+        return {k: v for k, v in self._zkw_compiled.items() if k in ("zero_node", "zero_edge")}
 
-    def compile(self, device, unrotate: bool, skip_weight=None):
+    def _ztag(self, n=3):
+        z = self._zkw_compiled
+        return ((z.get("zero_node", ()), z.get("zero_edge", ()), z.get("dead_out", ()))[:n],)
+
+    def _upload(self, key, tag, build, upload, uses_skip=False, sd=None, host=None):
+        """build the program `key` and upload it; sd: the state dict if the caller has just read it, None: read here -- always the weights of the
+        MOMENT (the programs uploaded before may have been refreshed since compile()); host: what `build` returns for them, if the caller has it already"""
+        if host is None:
+            skip = self._skip_weight if uses_skip else None
+            if sd is None:
+                sd = _np_sd(self)
+                if skip is not None and self._skip_source is not None:
+                    skip = self._skip_source[0].weight.detach().cpu().double().numpy()
+            host = build(sd, skip)
+        self._programs[key] = _Uploaded(upload(host), tag, build, uses_skip)
+        return self._programs[key].dev
+
+    def _upload_forward(self, reduced: bool, plain: bool, sd=None):
+        """reduced: the program that assumes _zkw_compiled; plain: without merged row tiles (the twin that split launches run)"""
+        zkw = self._zkw_compiled if reduced else {}
+        groups = () if plain else (self._groups_z if reduced else self._groups)
+        irr, unrotate, device = self._irreps, self._unrotate, self._device
+        has_skip = self._skip_weight is not None
+        schedule = "is" if self._groups else _mp_kernel()      # (a block compiled with merged row tiles has no segment-stationary form)
+        return self._upload(("forward", reduced, plain), ("fwd", unrotate, has_skip, bool(groups)) + (self._ztag() if reduced else ()),
+                            lambda sd, sk: P.build_message_pack_program(sd, *irr, unrotate, sk, merge_groups=groups, **zkw),
+                            lambda prog: ops.DeviceProgram(prog, device, schedule=schedule), uses_skip=has_skip, sd=sd)
+
+    def compile(self, device, unrotate: bool, skip_weight=None, skip_source=None):
+        """skip_weight: the flat weight of a PairInteractionBlock's skip o3.Linear, fused as extra items; skip_source: (that Linear,) -- the weight of
+        the moment for programs built after a refresh()"""
         sd = _np_sd(self)
-        zkw = self._zero_kw()
-        self._zkw_compiled = dict(zkw)                         # what the reduced program of THIS compile assumes (callers plan with it, not with the environment of the moment)
-        self._dp_z = self._dp_z_plain = None                    # programs for rows with structurally zero irreps (set_structural_zeros), built next to the generic ones
-        self._compile_args = (bool(unrotate), skip_weight is not None, None)      # (unrotate, fused skip Linear, merge groups)
-        self._lite_bw = None
-        self._packers = getattr(self, "_packers", None) or {}                     # structural: survive recompiles of the same block
-        self._dp_adj = self._dp_adj_z = None                   # the data-gradient programs are packed from the same weights
-        self._wgrad_prev, self._wgrad = (getattr(self, "_wgrad", None) or getattr(self, "_wgrad_prev", None)), None
-        self._wgrad_fused = self._wgrad_fused_z = None         # (tables hold the weights: rebuilt on first use)
+        self._reset(device, unrotate, skip_weight, skip_source)
+        zkw = self._zkw_compiled = self._zero_kw()
+        irr = self._irreps
         if self.lite_mode:
             if skip_weight is not None:                        # PairInteractionBlock skip o3.Linear: must come AFTER the combine post-op
                 raise NotImplementedError
             self._hn = self.weight_generator_combine.hidden_layers(device)
-            self._he = None
-            self._plain_args = None
-            if os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT) != "seg":
+            if _mp_kernel() != "seg":
                 # input-stationary kernel (r3): the paths of every (input irrep, output irrep) pair folded into one item (IT_LINM), the
                 # combine post-op as the last phase; such a program has no segment-stationary form
+                fold = os.environ.get("HG_LITE_FOLD", "1") != "0"
                 try:
-                    args = (sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate)
-                    self._dp = ops.DeviceProgram(P.build_message_pack_program_lite(*args, fold=os.environ.get("HG_LITE_FOLD", "1") != "0"), device, schedule="is")
+                    self._dp = self._upload(("forward", False, False), None, lambda sd, sk: P.build_message_pack_program_lite(sd, *irr, unrotate, fold=fold),
+                                            lambda prog: ops.DeviceProgram(prog, device, schedule="is"), sd=sd)
                     return self
                 except NotImplementedError:
                     pass
-            prog = P.build_message_pack_program_lite(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate)
-            self._dp = ops.DeviceProgram(prog, device, schedule="seg")
+            self._dp = self._upload(("forward", False, False), None, lambda sd, sk: P.build_message_pack_program_lite(sd, *irr, unrotate),
+                                    lambda prog: ops.DeviceProgram(prog, device, schedule="seg"), sd=sd)
             return self
-        else:
-            self._hn = self.node_weight_generator.hidden_layers(device)
-            self._he = self.edge_weight_generator.hidden_layers(device)
-            sched = os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT)
-            if sched != "seg" and os.environ.get("HG_MP_MERGE", "1") != "0":
-                # input-stationary kernel with the small output irreps sharing MFMA row tiles (plan.choose_merge_groups): -5 % MFMAs, -17 %
-                # items for set-A.  Such a program has no segment-stationary form: if it does not fit, fall back to the plain program.
-                groups = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, _hidden_width(self._hn))
-                if groups:
-                    try:
-                        prog = P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate,
-                                                            skip_weight, merge_groups=groups)
-                        self._dp = ops.DeviceProgram(prog, device, schedule="is")
-                        self._compile_args = (bool(unrotate), skip_weight is not None, groups)
-                        if zkw:                                # the same block for rows whose marked irreps are structurally zero (first layer of a backbone) /
-                            gz = groups                        # whose marked output irreps nobody reads (last PairInteractionBlock): those leave the row-tile groups
-                            if zkw.get("dead_out"):
-                                gz = P.choose_merge_groups(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, _hidden_width(self._hn), dead_out=zkw["dead_out"])
-                            self._groups_z = gz
-                            self._dp_z = ops.DeviceProgram(P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate,
-                                                                                       skip_weight, merge_groups=gz, **zkw), device, schedule="is")
-                        # launches with fewer 16-edge tiles than workgroup slots run the PLAIN program split over one workgroup per output
-                        # segment: merging trades parts (9 instead of 13 for set-A) for MFMAs, the wrong trade when latency is all there is
-                        # (Si 2-atom cell: 0.113 -> 0.110 ms per launch); built on first use
-                        self._plain_args = (sd, unrotate, skip_weight, device)
-                        self._dp_plain = None
-                        return self
-                    except NotImplementedError:
-                        pass
-            prog = P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate, skip_weight)
-            if zkw:
-                self._dp_z = ops.DeviceProgram(P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate, skip_weight, **zkw),
-                                               device, schedule=os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT))
-        self._plain_args = None
-        # HG_MP_KERNEL = seg | is | auto: which schedule of the fused MessagePackBlock program runs (default: see DESIGN.md section 5)
-        self._dp = ops.DeviceProgram(prog, device, schedule=os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT))
+        self._hn = self.node_weight_generator.hidden_layers(device)
+        self._he = self.edge_weight_generator.hidden_layers(device)
+        if _mp_kernel() != "seg" and os.environ.get("HG_MP_MERGE", "1") != "0":
+            # input-stationary kernel with the small output irreps sharing MFMA row tiles (plan.choose_merge_groups): -5 % MFMAs, -17 %
+            # items for set-A.  Such a program has no segment-stationary form: if it does not fit, fall back to the plain program.
+            # Launches with fewer 16-edge tiles than workgroup slots run the PLAIN twin split over one workgroup per output
+            # segment: merging trades parts (9 instead of 13 for set-A) for MFMAs, the wrong trade when latency is all there is
+            # (Si 2-atom cell: 0.113 -> 0.110 ms per launch); built on first use (_dp_for)
+            hidden = _hidden_width(self._hn)
+            self._groups = self._groups_z = P.choose_merge_groups(*irr, hidden)
+            if self._groups:
+                try:
+                    if zkw.get("dead_out"):                    # output irreps nobody reads leave the row-tile groups
+                        self._groups_z = P.choose_merge_groups(*irr, hidden, dead_out=zkw["dead_out"])
+                    self._dp = self._upload_forward(False, False, sd)
+                    if zkw:                                    # the same block for rows whose marked irreps are structurally zero (first layer of a backbone) /
+                        self._upload_forward(True, False, sd)  # whose marked output irreps nobody reads (last PairInteractionBlock)
+                    return self
+                except NotImplementedError:
+                    self._programs.clear()
+        self._groups = self._groups_z = ()
+        if zkw:
+            self._upload_forward(True, False, sd)
+        self._dp = self._upload_forward(False, False, sd)
         return self
 
     # ---- training: repack the weights of the uploaded programs on the device after an optimiser step (hamgnn_amd/repack.py)
     def refresh(self, skip=None) -> bool:
         """skip: the flat weight of the fused skip o3.Linear (device tensor) if the block was compiled with one.  Returns False when
-        there is nothing to refresh in place (never compiled, lite_mode): the caller compiles instead."""
+        there is nothing to refresh in place (never compiled, lite_mode, use_kan): the caller compiles instead."""
         from . import repack as RP
-        if self.lite_mode or self.use_kan or self._dp is None or getattr(self, "_compile_args", None) is None:
+        if self.lite_mode or self.use_kan or self._dp is None:
             return False
-        unrotate, has_skip, groups = self._compile_args
-        if has_skip != (skip is not None):
+        if (self._skip_weight is not None) != (skip is not None):
             return False
         params = {k: v.detach() for k, v in self.state_dict().items()}
         shapes = {k: tuple(v.shape) for k, v in params.items()}
         last = {n: sorted(k for k in params if k.startswith(f"{n}_weight_generator.layer") and k.endswith(".weight"))[-1] for n in ("node", "edge")}
-        lays = RP.mp_branch_layouts(self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out)
-        args = (self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out)
+        lays = RP.mp_branch_layouts(*self._irreps)
         nskip = int(skip.numel()) if skip is not None else 0
         lp = None
-        dev0 = self._dp.weights.device
+        dev = self._dp.weights.device
         if ops.use_block_gemm(self._dp.weights):               # the 13 L' products of a branch in ONE launch (csrc/block_gemm.hip) instead of 13 GEMMs
-            if getattr(self, "_bg_lp", None) is None or self._bg_lp[0] != dev0:
-                self._bg_lp = (dev0, {name: (ops.BlockGemm(RP.lp_block_units(lay)[0], dev0), RP.lp_block_units(lay)[1]) for name, lay in lays})
+            if self._bg_lp is None or self._bg_lp[0] != dev:
+                self._bg_lp = (dev, {name: (ops.BlockGemm(RP.lp_block_units(lay)[0], dev), RP.lp_block_units(lay)[1]) for name, lay in lays})
             lp = {}
             for name, (bg, total) in self._bg_lp[1].items():
                 ls, lo = params[f"{name}_linear_scaler.linear_out.weight"].float().reshape(-1).contiguous(), params[f"{name}_linear_out.weight"].float().reshape(-1).contiguous()
-                lp[name] = ops.block_gemm(bg, ls, lo, torch.empty(total, device=dev0, dtype=torch.float64))
+                lp[name] = ops.block_gemm(bg, ls, lo, torch.empty(total, device=dev, dtype=torch.float64))
         src = RP.mp_sources(lambda k: params[k].double().reshape(-1), last, lays, None if skip is None else skip.detach().double().reshape(-1), lib=torch, lp=lp)
-
-        def packer(tag, fn, ns):
-            if tag not in self._packers:
-                sizes = RP.mp_source_sizes(shapes, last, ns)
-                self._packers[tag] = RP.AffinePack(lambda d: fn(RP.mp_probe_state_dict(d, shapes, last, lays, self.irreps_out), d.get("skip")), sizes)
-            return self._packers[tag]
-
-        def update(dp, tag, fn, ns):
-            blob = packer(tag, fn, ns).apply({k: v for k, v in src.items() if ns or k != "skip"})
-            assert blob.numel() == dp.weights.numel(), (tag, blob.numel(), dp.weights.numel())
-            dp.weights.copy_(blob)
-            dp.weights_changed()
-
-        zkw = self._zero_kw()
-        ztag = (zkw.get("zero_node", ()), zkw.get("zero_edge", ()), zkw.get("dead_out", ()))
-        fwd = lambda g_, z_=None: (lambda d, sk: P.build_message_pack_program(d, *args, unrotate, sk, **({"merge_groups": g_} if g_ else {}), **(z_ or {})).weights)
-        update(self._dp, ("fwd", unrotate, has_skip, bool(groups)), fwd(groups), nskip)
-        if getattr(self, "_dp_plain", None) is not None and self._dp_plain is not self._dp:
-            update(self._dp_plain, ("fwd", unrotate, has_skip, False), fwd(None), nskip)
-        if getattr(self, "_dp_z", None) is not None:
-            gz = getattr(self, "_groups_z", groups) if groups else groups
-            update(self._dp_z, ("fwd", unrotate, has_skip, bool(gz), ztag), fwd(gz, zkw), nskip)
-        if getattr(self, "_dp_z_plain", None) is not None and self._dp_z_plain is not self._dp_z:
-            update(self._dp_z_plain, ("fwd", unrotate, has_skip, False, ztag), fwd(None, zkw), nskip)
-        if getattr(self, "_dp_adj", None) is not None:
-            update(self._dp_adj, ("adj",), lambda d, sk: P.build_message_pack_adjoint_program(d, *args).weights, 0)
-        zin = self._zero_inputs_kw()
-        if getattr(self, "_dp_adj_z", None) is not None:
-            update(self._dp_adj_z, ("adj", ztag[:2]), lambda d, sk: P.build_message_pack_adjoint_program(d, *args, **zin).weights, 0)
-        if getattr(self, "_wgrad", None) is not None:
-            wg, dpA, dpB = self._wgrad
-            if dpA is not None:
-                update(dpA, ("wgA",), lambda d, sk: P.build_message_pack_wgrad_programs(d, *args)[0].weights, 0)
-                update(dpB, ("wgB",), lambda d, sk: P.build_message_pack_wgrad_programs(d, *args)[1].weights, 0)
-            wg.params_dev = params                             # the radial MLP / Ls / Lo values that the reductions read: straight from the device
-            dwf = getattr(self, "_wgrad_fused", None)
-            if dwf:
-                irr = (self.irreps_node, self.irreps_edge)
-                fused = lambda d, sk: P.build_tp_wgrad_fused(P.message_pack_wgrad_branches(d, *irr), self.irreps_sh, self.irreps_out, dwf.wf.hidden).weights
-                dwf.weights.copy_(packer(("wgF",), fused, 0).apply({k: v for k, v in src.items() if k != "skip"}))
-            dwz = getattr(self, "_wgrad_fused_z", None)
-            if dwz:
-                irr = (self.irreps_node, self.irreps_edge)
-                zi = {"node": zin.get("zero_node", ()), "edge": zin.get("zero_edge", ())}
-                fused_z = lambda d, sk: P.build_tp_wgrad_fused(P.message_pack_wgrad_branches(d, *irr), self.irreps_sh, self.irreps_out, dwz.wf.hidden, zero_inputs=zi).weights
-                dwz.weights.copy_(packer(("wgF", ztag[:2]), fused_z, 0).apply({k: v for k, v in src.items() if k != "skip"}))
-        dev = self._dp.weights.device
+        for e in {id(e): e for e in self._programs.values() if e.dev is not None}.values():       # (a plain twin that did not fit IS its merged sibling: repacked once)
+            ns = nskip if e.uses_skip else 0
+            if e.tag not in self._packers:
+                probe = lambda d, build=e.build: build(RP.mp_probe_state_dict(d, shapes, last, lays, self.irreps_out), d.get("skip")).weights
+                self._packers[e.tag] = RP.AffinePack(probe, RP.mp_source_sizes(shapes, last, ns))
+            blob = self._packers[e.tag].apply({k: v for k, v in src.items() if ns or k != "skip"})
+            assert blob.numel() == e.dev.weights.numel(), (e.tag, blob.numel(), e.dev.weights.numel())
+            e.dev.weights.copy_(blob)
+            if isinstance(e.dev, ops.DeviceProgram):           # (the edge programs derive the split W3 twins from the blob)
+                e.dev.weights_changed()
+        if self._wg is not None:
+            self._wg.params_dev = params                    # the radial MLP / Ls / Lo values that the reductions read: straight from the device
         self._hn = self.node_weight_generator.hidden_layers(dev)
         self._he = self.edge_weight_generator.hidden_layers(dev)
         return True
@@ -480,15 +505,22 @@ class MessagePackBlock(nn.Module):
         if self.lite_mode:
             raise NotImplementedError("data gradient of a lite_mode MessagePackBlock")
         zin = self._zero_inputs_kw() if structural_zeros else {}
-        prog = P.build_message_pack_adjoint_program(_np_sd(self), self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, **zin)
-        try:
-            dp = ops.DeviceProgram(prog, device, schedule="is_parts" if os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT) != "seg" else "seg")
-        except NotImplementedError:                            # tiles / staging do not fit even split over workgroups: segment-stationary kernel
-            dp = ops.DeviceProgram(prog, device, schedule="seg")
-        setattr(self, "_dp_adj_z" if zin else "_dp_adj", dp)
+        irr = self._irreps
+        self._upload(("adjoint", bool(zin)), ("adj",) + (self._ztag(2) if zin else ()), lambda sd, sk: P.build_message_pack_adjoint_program(sd, *irr, **zin),
+                     lambda prog: _upload_adjoint(prog, device))
         _, maps = P.message_pack_adjoint_layout(self.irreps_node, self.irreps_edge)
         self._adj_maps = tuple(torch.from_numpy(m).to(device) for m in maps)
         return self
+
+    def _hidden(self, geo: ops.Geometry):
+        """(node, edge) rows that the edge kernels multiply with the last layer of the two weight generators (lite_mode: one generator, edge None)"""
+        return _hidden_rows(geo, self._hn), (_hidden_rows(geo, self._he) if self._he is not None else None)
+
+    def _edge_frame(self, grad_out, gather, geo: ops.Geometry, out_is_global: bool):
+        """the gradient of the block's output rows per edge, in the edge frame (frame and `gather` as in backward_data)"""
+        if out_is_global:
+            return ops.rotate_gather(grad_out, gather, geo, self._rot_tab_out(grad_out.device))
+        return grad_out if gather is None else grad_out[gather].contiguous()
 
     def backward_data(self, grad_out, geo: ops.Geometry, out_is_global: bool, gather=None, structural_zeros: bool = False):
         """grad_out [E, planar(irreps_out)]: gradient with respect to the rows this block's forward returned (global frame if the block
@@ -499,21 +531,14 @@ class MessagePackBlock(nn.Module):
         receiver CSR) for the gradient of the gathered node rows; the third in the edge frame, where the forward read the edge rows."""
         _no_kan_backward(self.use_kan, "the data gradient of a MessagePackBlock")
         z = bool(structural_zeros and self._zero_inputs_kw())   # (the caller vouches as for run_nodes: the marked input irreps are zero, their gradient unread)
-        slot = "_dp_adj_z" if z else "_dp_adj"
-        if getattr(self, slot, None) is None:
+        if ("adjoint", z) not in self._programs:
             self.compile_adjoint(grad_out.device, structural_zeros=z)
-        cst = float(P.ACT_CONSTS[P.ACT_SILU])
-        hn = ops.radial_hidden_cached(geo, self._hn, cst)
-        he = ops.radial_hidden_cached(geo, self._he, cst)
-        dp = getattr(self, slot)
+        hn, he = self._hidden(geo)
+        dp = self._programs[("adjoint", z)].dev
         if dp.sched is not None:
             g = ops.tp_fused(dp, [grad_out], geo.E, hn, he, geo, tag="message_pack_adjoint", gather=[gather], rot_mask=1 if out_is_global else 0)
         else:
-            if out_is_global:
-                src = ops.rotate_gather(grad_out, gather, geo, self._rot_tab_out(grad_out.device))
-            else:
-                src = grad_out if gather is None else grad_out[gather].contiguous()
-            g = ops.tp_fused(dp, [src], geo.E, hn, he, geo, tag="message_pack_adjoint")
+            g = ops.tp_fused(dp, [self._edge_frame(grad_out, gather, geo, out_is_global)], geo.E, hn, he, geo, tag="message_pack_adjoint")
         ims, imd, ime = self._adj_maps
         return ops.from_planar(g, ims), ops.from_planar(g, imd), ops.from_planar(g, ime)      # column gathers (-1 = padding slot -> 0)
 
@@ -521,22 +546,16 @@ class MessagePackBlock(nn.Module):
         """the program a launch of `rows` edges runs: the merged one, or -- split launches of small crystals -- the plain one; structural_zeros: the caller
         vouches that the irreps marked by set_structural_zeros are zero in the rows it passes (the backbone's first layer) AND that nobody reads the output
         irreps marked by set_dead_outputs (they come back as zeros): the reduced program"""
-        z = structural_zeros and getattr(self, "_dp_z", None) is not None
-        dp = self._dp_z if z else self._dp
-        if getattr(self, "_plain_args", None) is None or dp.is_parts_for(rows) == 1:
+        z = bool(structural_zeros and ("forward", True, False) in self._programs)
+        dp = self._programs[("forward", z, False)].dev
+        if not self._groups or dp.is_parts_for(rows) == 1:
             return dp
-        slot = "_dp_z_plain" if z else "_dp_plain"
-        if getattr(self, slot, None) is None:
-            _, unrotate, skip_weight, device = self._plain_args
-            sd = _np_sd(self)                                  # the CURRENT weights (the merged program may have been refreshed since compile())
-            if skip_weight is not None and getattr(self, "_skip_source", None) is not None:
-                skip_weight = self._skip_source[0].weight.detach().cpu().double().numpy()
-            prog = P.build_message_pack_program(sd, self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out, unrotate, skip_weight, **(self._zero_kw() if z else {}))
+        if ("forward", z, True) not in self._programs:
             try:
-                setattr(self, slot, ops.DeviceProgram(prog, device, schedule="is"))
+                self._upload_forward(z, True)
             except NotImplementedError:
-                setattr(self, slot, dp)
-        return getattr(self, slot)
+                self._programs[("forward", z, True)] = self._programs[("forward", z, False)]
+        return self._programs[("forward", z, True)].dev
 
     def backward_weights(self, node_s, node_d, f_rot, geo: ops.Geometry, rot_tab, grad_out, out_is_global: bool, chunk: int = 65536, gather=None,
                          structural_zeros: bool = False):
@@ -549,46 +568,49 @@ class MessagePackBlock(nn.Module):
         if self.lite_mode:
             raise NotImplementedError("weight gradients of a lite_mode MessagePackBlock")
         dev = grad_out.device
-        if getattr(self, "_wgrad", None) is None:
-            wg = BM.MessagePackWeightGrad(_np_sd(self), self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out)
-            wg.adopt_constants(self._wgrad_prev[0] if getattr(self, "_wgrad_prev", None) else None)
-            wg.params_dev = {k: v.detach() for k, v in self.state_dict().items()}
-            self._wgrad = [wg, None, None]
-        wg, dpA, dpB = self._wgrad
+        if self._wg is None:
+            self._wg = BM.MessagePackWeightGrad(_np_sd(self), *self._irreps).adopt_constants(self._wg_prev)
+            self._wg.params_dev = {k: v.detach() for k, v in self.state_dict().items()}
+        wg = self._wg
         xs, xd = ops.rotate_gather(node_s, geo.src, geo, rot_tab, x2=node_d, idx2=geo.dst)
-        if out_is_global:
-            g = ops.rotate_gather(grad_out, gather, geo, self._rot_tab_out(dev))
-        else:
-            g = grad_out if gather is None else grad_out[gather].contiguous()
+        g = self._edge_frame(grad_out, gather, geo, out_is_global)
         cst = float(P.ACT_CONSTS[P.ACT_SILU])
         dwf = self._wgrad_fused_for(wg, dev, structural_zeros)
         if dwf is not None:                                    # fused kernel (csrc/tp_wgrad.hip): nothing per edge is materialised but gs
-            hidden = {"node": ops.radial_hidden_cached(geo, self._hn, cst), "edge": ops.radial_hidden_cached(geo, self._he, cst)}
+            hidden = dict(zip(("node", "edge"), self._hidden(geo)))
             run = lambda srcs, g_, hn, he: ops.tp_wgrad(dwf, srcs, g_, hn, he)
             return BM.tp_weight_grads_fused(wg, dwf, run, [xs, xd, f_rot], g, geo.rbf, cst, hidden=hidden)     # dwf: the gather maps as device tensors
-        if dpA is None:                                        # materialisation route: the two row programs on the segment-stationary kernel
-            dpA, dpB = ops.DeviceProgram(wg.progA, dev, schedule="seg"), ops.DeviceProgram(wg.progB, dev, schedule="seg")
-            self._wgrad[1:] = [dpA, dpB]
+        if ("wgrad rows", "A") not in self._programs:          # materialisation route: the two row programs on the segment-stationary kernel
+            irr = self._irreps
+            pair = P.build_message_pack_wgrad_programs(_np_sd(self), *irr)      # (one planner run builds both)
+            for i, ab in enumerate("AB"):
+                self._upload(("wgrad rows", ab), ("wg" + ab,), lambda sd, sk, i=i: P.build_message_pack_wgrad_programs(sd, *irr)[i],
+                             lambda prog: ops.DeviceProgram(prog, dev, schedule="seg"), host=pair[i])
+        dpA, dpB = self._programs[("wgrad rows", "A")].dev, self._programs[("wgrad rows", "B")].dev
         return BM.block_weight_grads(wg, _wgrad_runner(wg, dpA, dpB), xs, xd, f_rot, g, geo.rbf, cst, chunk=chunk)
 
     def _wgrad_fused_for(self, wg, dev, structural_zeros: bool = False):
         """the fused weight-gradient tables of this block on the device, or None (HG_WGRAD=rows, or no kernel instantiation for these irreps:
         the materialisation route then).  structural_zeros: the tables without the row tiles of super-paths that read structurally zero input irreps
-        (their gradients are exactly zero: plan.build_tp_wgrad_fused)"""
+        (their gradients are exactly zero: plan.build_tp_wgrad_fused).  wg: the block's weight-gradient holder, part of the signature callers outside the class
+        were written against; the tables are built from the weights of the moment, not from what `wg` captured"""
         if os.environ.get("HG_WGRAD", "fused") != "fused":
             return None
         zin = self._zero_inputs_kw() if structural_zeros else {}
-        slot = "_wgrad_fused_z" if zin else "_wgrad_fused"
-        cur = getattr(self, slot, None)
-        if cur is None:
+        key = ("wgrad fused", bool(zin))
+        if key not in self._programs:
+            zi = {"node": zin.get("zero_node", ()), "edge": zin.get("zero_edge", ())} if zin else None
+            irr = self._irreps
+
+            def build(sd, sk):
+                br = P.message_pack_wgrad_branches(sd, irr[0], irr[1])
+                return P.build_tp_wgrad_fused(br, irr[2], irr[3], int(br[0]["w3"].shape[0]), zero_inputs=zi)
+            tag = ("wgF",) + (self._ztag(2) if zin else ())
             try:
-                zi = {"node": zin.get("zero_node", ()), "edge": zin.get("zero_edge", ())} if zin else None
-                wf = P.build_tp_wgrad_fused(wg.branches, self.irreps_sh, self.irreps_out, wg.H, zero_inputs=zi)
-                cur = ops.DeviceWgFused(wf, dev)
+                self._upload(key, tag, build, lambda wf: ops.DeviceWgFused(wf, dev))
             except NotImplementedError:
-                cur = False
-            setattr(self, slot, cur)
-        return cur or None
+                self._programs[key] = _Uploaded(None, tag, build, False)
+        return self._programs[key].dev
 
     def backward(self, node_s, node_d, f_rot, geo: ops.Geometry, rot_tab, grad_out, out_is_global: bool, gather=None, chunk: int = 65536,
                  structural_zeros: bool = False):
@@ -602,23 +624,15 @@ class MessagePackBlock(nn.Module):
             return self.backward_data(grad_out, geo, out_is_global, gather=gather, structural_zeros=structural_zeros) + (grads,)
         from . import backward_lite as BL
         dev = grad_out.device
-        if getattr(self, "_lite_bw", None) is None:
-            lb = BL.LiteBackward(_np_sd(self), self.irreps_node, self.irreps_edge, self.irreps_sh, self.irreps_out)
-            dp_t = ops.DeviceProgram(lb.prog_t, dev, schedule="seg")
-            try:
-                dp_a = ops.DeviceProgram(lb.prog_adj, dev, schedule="is_parts" if os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT) != "seg" else "seg")
-            except NotImplementedError:
-                dp_a = ops.DeviceProgram(lb.prog_adj, dev, schedule="seg")
+        if self._lite_bw is None:
+            lb = BL.LiteBackward(_np_sd(self), *self._irreps)
+            dps = {id(lb.prog_t): ops.DeviceProgram(lb.prog_t, dev, schedule="seg"), id(lb.prog_adj): _upload_adjoint(lb.prog_adj, dev)}
             _, maps = P.message_pack_adjoint_layout(self.irreps_node, self.irreps_edge)
-            self._lite_bw = (lb, {id(lb.prog_t): dp_t, id(lb.prog_adj): dp_a}, ops.DeviceLinear(lb.lc_adj, dev),
-                             tuple(torch.from_numpy(m).to(dev) for m in maps))
+            self._lite_bw = (lb, dps, ops.DeviceLinear(lb.lc_adj, dev), tuple(torch.from_numpy(m).to(dev) for m in maps))
         lb, dps, dl, maps = self._lite_bw
         xs, xd = ops.rotate_gather(node_s, geo.src, geo, rot_tab, x2=node_d, idx2=geo.dst)
-        if out_is_global:
-            g = ops.rotate_gather(grad_out, gather, geo, self._rot_tab_out(dev))
-        else:
-            g = grad_out if gather is None else grad_out[gather].contiguous()
-        hn = ops.radial_hidden_cached(geo, self._hn, float(P.ACT_CONSTS[P.ACT_SILU]))   # (no item of the two programs reads it; never hand the kernel a NULL row pointer)
+        g = self._edge_frame(grad_out, gather, geo, out_is_global)
+        hn, _ = self._hidden(geo)                              # (no item of the two programs reads it; never hand the kernel a NULL row pointer)
         run_program = lambda prog, srcs: ops.tp_fused(dps[id(prog)], [t.contiguous() for t in srcs], geo.E, hn, None, geo, tag="lite_backward")
         run_linear = lambda tabs, x: ops.linear_planar(dl, x.contiguous(), tag="linear_adjoint")
         rows, grads = lb.run(run_program, run_linear, o3_linear_weight_grad, xs, xd, f_rot, g, geo.rbf, float(P.ACT_CONSTS[P.ACT_SILU]),
@@ -626,14 +640,13 @@ class MessagePackBlock(nn.Module):
         return ops.from_planar(rows, maps[0]), ops.from_planar(rows, maps[1]), ops.from_planar(rows, maps[2]), grads
 
     def _rot_tab_out(self, device):
-        if getattr(self, "_rt_out", None) is None:
+        if self._rt_out is None:
             self._rt_out = torch.from_numpy(P.rotate_table(P.PlanarLayout(self.irreps_out))).to(device)
         return self._rt_out
 
     def run(self, xs_rot, xd_rot, f_rot, geo: ops.Geometry):
         """xs_rot/xd_rot/f_rot: planar rows in the edge-aligned frame.  Returns planar [E, Dp] (global frame if unrotate)."""
-        hn = _hidden_rows(geo, self._hn)
-        he = _hidden_rows(geo, self._he) if self._he is not None else None
+        hn, he = self._hidden(geo)
         return ops.tp_fused(self._dp_for(geo.E), [xs_rot, xd_rot, f_rot], geo.E, hn, he, geo, tag="message_pack")
 
     def can_reduce(self, rows: int) -> bool:
@@ -647,8 +660,7 @@ class MessagePackBlock(nn.Module):
         if self._dp.sched is None:
             xs, xd = ops.rotate_gather(node_s, geo.src, geo, rot_tab, x2=node_d, idx2=geo.dst)
             return self.run(xs, xd, f_rot, geo)
-        hn = _hidden_rows(geo, self._hn)
-        he = _hidden_rows(geo, self._he) if self._he is not None else None
+        hn, he = self._hidden(geo)
         return ops.tp_fused(self._dp_for(geo.E, structural_zeros), [node_s, node_d, f_rot], geo.E, hn, he, geo, tag="message_pack", gather=[geo.src, geo.dst, None],
                             rot_mask=0b011, reduce=reduce)
 
@@ -894,8 +906,8 @@ class PairInteractionBlock(nn.Module):
             if self.use_skip_connections:
                 self.skip_linear.compile(device)
         else:
-            self.conv_tp._skip_source = (self.skip_linear,) if self.use_skip_connections else None   # (a tuple: not registered as a sub-module)
-            self.conv_tp.compile(device, unrotate=False, skip_weight=skip)   # skip o3.Linear fused as extra items
+            self.conv_tp.compile(device, unrotate=False, skip_weight=skip,   # skip o3.Linear fused as extra items
+                                 skip_source=(self.skip_linear,) if self.use_skip_connections else None)
             if self.use_skip_connections:
                 self.skip_linear._stale = True                 # its forward is fused above; only the backward uses the module's own (adjoint) tables
 
@@ -958,6 +970,9 @@ class PairInteractionEmbeddingBlock(nn.Module):
         self.linear_up_src = E3Linear(attrs, attrs)
         self.linear_up_dst = E3Linear(attrs, attrs)
         self.conv_tp = _EmbTP(attrs, self.irreps_sh, self.irreps_out, num_radial, radial_MLP, lite_mode, use_kan)
+        self._dp = self._h = self._sd_np = None                # set by compile()
+        self._wgrad = self._wgrad_prev = None                  # [backward_mp.TPWeightGrad, its two materialisation programs] of the compiled weights, and the one before
+        self._fused_bw = None                                  # (the TPWeightGrad they belong to, fused weight-gradient tables, adjoint program)
 
     def compile(self, device):
         T = self.num_types
@@ -970,7 +985,7 @@ class PairInteractionEmbeddingBlock(nn.Module):
         self._dp = ops.DeviceProgram(P.build_embedding_program(self._sd_np, T, self.irreps_sh, self.irreps_out, self.lite_mode), device)
         self._h = self.conv_tp.weight_generator.hidden_layers(device)
         self._Tp = P.PlanarLayout([(T, 0, 1)]).dim
-        self._wgrad_prev, self._wgrad = (getattr(self, "_wgrad", None) or getattr(self, "_wgrad_prev", None)), None
+        self._wgrad_prev, self._wgrad = (self._wgrad or self._wgrad_prev), None     # (device constants handed over: adopt_constants)
 
     def backward(self, z, geo: ops.Geometry, g_f, chunk: int = 65536, delta=None):
         """gradients of every parameter of the block for the gradient g_f of the edge rows it returned (planar, edge frame):
@@ -982,9 +997,9 @@ class PairInteractionEmbeddingBlock(nn.Module):
         _no_kan_backward(self.use_kan, "the backward of the pair embedding")
         dev, T = g_f.device, self.num_types
         if self._wgrad is None:
-            sd = getattr(self, "_sd_np", None) or _np_sd(self.conv_tp)
+            sd = self._sd_np
             wg = BM.TPWeightGrad(sd, P.embedding_wgrad_branches(sd, T, self.lite_mode), self.irreps_sh, self.irreps_out)
-            wg.adopt_constants(self._wgrad_prev[0] if getattr(self, "_wgrad_prev", None) else None)
+            wg.adopt_constants(self._wgrad_prev[0] if self._wgrad_prev else None)
             self._wgrad = [wg, None, None]                     # (the two materialisation programs are uploaded only if the fused route below is not available)
         wg, dpA, dpB = self._wgrad
         if delta is not None:
@@ -1028,16 +1043,12 @@ class PairInteractionEmbeddingBlock(nn.Module):
         that is not 64 wide, num_types not a multiple of 8 -- the materialisation route then.  Rebuilt when compile() replaced the weights."""
         if self.lite_mode or os.environ.get("HG_WGRAD", "fused") != "fused":
             return None
-        cur = getattr(self, "_fused_bw", None)
+        cur = self._fused_bw
         if cur is None or cur[0] is not wg:
             sd = wg.sd
             try:
                 wf = P.build_tp_wgrad_fused(P.embedding_wgrad_branches_split(sd, self.num_types), self.irreps_sh, self.irreps_out, wg.H)
-                prog = P.build_embedding_adjoint_program(sd, self.num_types, self.irreps_sh, self.irreps_out)
-                try:
-                    dp = ops.DeviceProgram(prog, dev, schedule="is_parts" if os.environ.get("HG_MP_KERNEL", MP_KERNEL_DEFAULT) != "seg" else "seg")
-                except NotImplementedError:
-                    dp = ops.DeviceProgram(prog, dev, schedule="seg")
+                dp = _upload_adjoint(P.build_embedding_adjoint_program(sd, self.num_types, self.irreps_sh, self.irreps_out), dev)
                 cur = (wg, ops.DeviceWgFused(wf, dev), dp)
             except NotImplementedError:
                 cur = (wg, None, None)

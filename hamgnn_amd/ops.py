@@ -535,9 +535,9 @@ def tp_fused(dp: DeviceProgram, srcs: List[torch.Tensor], rows: int, h2n=None, h
     assert len(res) <= 2 and (not res or dp.sched is None)
     for r in res:
         assert r.shape == (rows, dp.out_dim) and r.stride(1) == 1
-    assert reduce is None or (dp.sched is not None and dp.is_parts_for(rows) == 1)
-    parts_ = dp.is_parts_for(rows) if (dp.sched is not None and reduce is None) else 1
-    alloc = torch.zeros if isinstance(parts_, tuple) else torch.empty  # (the 2d split ADDS its tiles into zero-filled rows: plan.is_schedule ("2d", P, K))
+    parts = dp.is_parts_for(rows) if dp.sched is not None else 1       # decided ONCE per launch (it reads the environment): the allocation, the tables and the weights agree
+    assert reduce is None or (dp.sched is not None and parts == 1)
+    alloc = torch.zeros if isinstance(parts, tuple) else torch.empty  # (the 2d split ADDS its tiles into zero-filled rows: plan.is_schedule ("2d", P, K))
     out = alloc(rows if reduce is None else reduce[2], dp.out_dim, device=srcs[0].device, dtype=torch.float32)      # the kernel writes every slot incl. zero channel padding
     n = len(srcs)
     sp = (C.c_void_p * 4)(*([s.data_ptr() for s in srcs] + [0] * (4 - n)))
@@ -549,11 +549,10 @@ def tp_fused(dp: DeviceProgram, srcs: List[torch.Tensor], rows: int, h2n=None, h
     if dp.sched is not None:
         check_build_config()
         check_w3_split()
-    if dp.sched is not None:
-        sc, (t_segs, t_blocks, t_phases, t_groups, t_items, t_parts, t_rowtab) = dp.is_tables(dp.is_parts_for(rows))
+        sc, (t_segs, t_blocks, t_phases, t_groups, t_items, t_parts, t_rowtab) = dp.is_tables(parts)
         gl = list(gather) + [None] * (4 - len(gather)) if gather is not None else [None] * 4
         gp = (C.c_void_p * 4)(*[(t.data_ptr() if t is not None else 0) for t in gl])
-        check(lib().hg_tp_is(sp, ss, i32(n), ptr(h2n), ptr(h2e), i32(dp.hidden), wig, i32(nW), woff, ptr(dp.is_weights(dp.is_parts_for(rows))), ptr(t_segs),
+        check(lib().hg_tp_is(sp, ss, i32(n), ptr(h2n), ptr(h2e), i32(dp.hidden), wig, i32(nW), woff, ptr(dp.is_weights(parts)), ptr(t_segs),
                              ptr(t_blocks), ptr(t_phases), ptr(t_groups), ptr(t_items), ptr(t_parts),
                              np.ascontiguousarray(dp.part_table_host(sc)).ctypes.data_as(C.c_void_p), i32(sc.part_table.shape[0]), ptr(t_rowtab),
                              i32(sc.lds_floats * 4), gp, i32(rot_mask), ptr(reduce[0]) if reduce is not None else C.c_void_p(0),

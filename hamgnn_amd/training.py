@@ -214,7 +214,7 @@ def _invalidate(module):
             m._stale = True                                    # its tables are refreshed on the device at the next use (nn.E3Linear.compile)
             continue
         for attr in ("_dp", "_dp_adj", "_adj_tabs"):             # (`_wgrad` is handed over by the blocks' compile(): its device constants are reused)
-            if hasattr(m, attr):
+            if attr in vars(m):                                # (an attribute the instance holds, not a read-only view of its class)
                 setattr(m, attr, None)
         if hasattr(m, "_rowprog"):                             # HamLayer's fused inference chain: its 0.1 s host build per step is not worth it while
             m._rowprog = None                                  # the weights move (the backward re-evaluates the stages one by one anyway)

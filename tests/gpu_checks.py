@@ -253,7 +253,7 @@ def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedu
     try:
         m.compile_adjoint(device)
         gs, gd, gf = m.backward_data(ops.to_planar(G.float().to(device), imap, lay.dim), geo, out_is_global=True, gather=geo.dst if gather else None)
-        dpa = m._dp_adj
+        dpa = m.programs()[("adjoint", False)]
         parts_used = dpa.is_parts_for(E) if dpa.sched is not None else 0       # what the launch above asked the schedule for (an int, or "lds")
     finally:
         os.environ.pop("HG_MP_KERNEL", None)
@@ -336,8 +336,7 @@ def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=
     torch.cuda.synchronize()
     assert set(got) == set(want), sorted(set(got) ^ set(want))[:4]
     errs = {k: metric(got[k], want[k]) for k in want}
-    wgs = getattr(m, "_wgrad", None)
-    dwf = m._wgrad_fused_for(wgs[0], got[next(iter(got))].device) if wgs else None          # (cached by backward_weights: the tables that call ran, or None)
+    dwf = m.programs().get(("wgrad fused", False))              # (uploaded by backward_weights: the tables that call ran, or None)
     res = {"irreps": irr, "sh": sh, "E": E, "max_rel_err": max(errs.values()), "worst": max(errs, key=errs.get), "fused_route": dwf is not None,
            "nsplit": dwf.nsplit_for(E) if dwf is not None else 0}
     if fp32_ref:
@@ -547,18 +546,24 @@ def check_full_training(device="cuda", steps=12):
     return {"first": losses[0], "last": losses[-1], "losses": losses}
 
 
-def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=False):
+# MessagePackBlock.programs(): forward, forward plain, reduced, reduced plain; adjoint, adjoint reduced; wgrad fused, wgrad fused reduced
+MESSAGE_PACK_PROGRAM_KINDS = [("forward", False, False), ("forward", False, True), ("forward", True, False), ("forward", True, True),
+                              ("adjoint", False), ("adjoint", True), ("wgrad fused", False), ("wgrad fused", True)]
+
+
+def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=False, radial=(16, 16), num_types=20):
     """training: after an optimiser step the message blocks repack their weights on the device (hamgnn_amd/repack.py).  A model that
     took a step, had ALL parameters perturbed and was refreshed must give the loss and every gradient of a freshly compiled model with
-    the same parameters."""
+    the same parameters.  radial=(16, 64), num_types=24: the fused weight-gradient route, with which a first-layer block holds every kind of
+    program -- "kinds" counts the backbone's message blocks that hold each at the moment the weights move, "embedding_fused_route" says that the pair embedding took it too."""
     import copy
     from hamgnn_amd.data import synthetic as S
     from hamgnn_amd.models.hamgnn_conv import HamGNNConvE3
     from hamgnn_amd.models.hamgnn_output import HamGNNPlusPlusOut
     from hamgnn_amd.models.model import Model
     from hamgnn_amd.training import training_step
-    cfg = dict(num_types=20, irreps_edge_sh=SH, edge_sh_normalization="component", edge_sh_normalize=True, build_internal_graph=False,
-               cutoff=26.0, rbf_func="bessel", num_radial=8, num_layers=2, irreps_node_features=MINI, use_kan=False, radial_MLP=[16, 16],
+    cfg = dict(num_types=num_types, irreps_edge_sh=SH, edge_sh_normalization="component", edge_sh_normalize=True, build_internal_graph=False,
+               cutoff=26.0, rbf_func="bessel", num_radial=8, num_layers=2, irreps_node_features=MINI, use_kan=False, radial_MLP=list(radial),
                correlation=2, num_hidden_features=4, use_corr_prod=False, legacy_edge_update=legacy)
     irr = "8x0e+4x0o+4x1o+2x1e+2x2o+4x2e+2x3o" if transformer else MINI
     if transformer:
@@ -575,6 +580,12 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
     with torch.no_grad():
         H_pre = a(g)["hamiltonian"].clone()                     # an INFERENCE forward first: builds the cached fused chains (ResidualBlock / HamLayer row programs)
     training_step(a, g, metric="mse", target=target)            # builds every program (forward, adjoint, weight-gradient), marks them stale
+    from hamgnn_amd.nn import MessagePackBlock
+    kinds = {}                                                  # what the BACKBONE's message blocks hold now, when the weights move: what refresh() has to repack
+    for m in a.representation.modules():
+        for k in (m.programs() if isinstance(m, MessagePackBlock) else ()):
+            kinds[k] = kinds.get(k, 0) + 1
+    fb = a.representation.pair_embedding._fused_bw
     gen = torch.Generator().manual_seed(4)
     with torch.no_grad():
         for p in a.parameters():                                # "the optimiser step"
@@ -583,7 +594,7 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
     b = mk().to(device)
     b.load_state_dict(copy.deepcopy(a.state_dict()))
     ra = training_step(a, g, metric="mse", target=target)
-    refreshed = sum(len(m._packers) for m in a.modules() if hasattr(m, "_packers"))
+    refreshed = sum(len(m._packers) for m in a.modules() if isinstance(m, MessagePackBlock))
     rb = training_step(b, g, metric="mse", target=target)
     # validate -> step -> validate: an inference forward of the stepped model must use the NEW weights everywhere, also in the chains that
     # were cached by the inference forward before the step
@@ -593,7 +604,7 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
     pa, pb = dict(a.named_parameters()), dict(b.named_parameters())
     worst = max(float((pa[k].grad - pb[k].grad).abs().max()) / max(float(pb[k].grad.abs().max()), 1e-6) for k in pb)
     return {"packers": refreshed, "loss_rel_diff": abs(float(ra["loss"]) - float(rb["loss"])) / abs(float(rb["loss"])), "grad_max_rel_diff": worst,
-            "inference_rel_diff": rel(Ha, Hb), "step_moved_H": rel(H_pre, Hb)}
+            "inference_rel_diff": rel(Ha, Hb), "step_moved_H": rel(H_pre, Hb), "kinds": kinds, "embedding_fused_route": fb is not None and fb[1] is not None}
 
 
 def check_conv_message_backward(device="cuda", n_atoms=10, seed=2):
@@ -636,7 +647,8 @@ def check_conv_message_backward(device="cuda", n_atoms=10, seed=2):
     fp = ops.rotate_gather(ops.to_planar(f.detach().float().to(device), imap, lay.dim), None, geo, rot)   # (unused by the linear adjoint; layout check only)
     gf = ops.rotate_gather(gf, None, geo, rot, transpose=True)
     torch.cuda.synchronize()
-    return {"N": N, "E": E, "parts": int(m._dp_adj.sched.part_table.shape[0]) if m._dp_adj.sched is not None else 0,
+    dpa = m.programs()[("adjoint", False)]
+    return {"N": N, "E": E, "parts": int(dpa.sched.part_table.shape[0]) if dpa.sched is not None else 0,
             "g_node_rel_err": rel(ops.from_planar(gx, imap), x.grad), "g_edge_rel_err": rel(ops.from_planar(gf, imap), f.grad)}
 
 
@@ -2798,16 +2810,16 @@ def check_structural_zeros_backward(device="cuda", n_atoms=40, legacy=False):
                 torch.cuda.synchronize()
             runs.append((out["loss"].detach().clone(), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}))
             mp = model.representation.convolutions[0].conv_tp
-            zslot = getattr(mp, "_wgrad_fused_z", None) or getattr(mp, "_wgrad_fused", None)
-            sizes.append((float(zslot.wf.mfma_per_tile) if zslot else 0.0, int(getattr(mp, "_dp_adj_z", None).prog.mfma_per_wave if getattr(mp, "_dp_adj_z", None) is not None
-                                                                                    else mp._dp_adj.prog.mfma_per_wave)))
+            held = mp.programs()
+            zslot = held.get(("wgrad fused", True)) or held.get(("wgrad fused", False))
+            sizes.append((float(zslot.wf.mfma_per_tile) if zslot else 0.0, int((held.get(("adjoint", True)) or held[("adjoint", False)]).prog.mfma_per_wave)))
         finally:
             os.environ.pop("HG_STRUCT_ZEROS", None)
     (l1, g1), (l0, g0) = runs
     errs = {k: float((g1[k].double() - g0[k].double()).abs().max() / max(float(g0[k].abs().max()), 1e-6)) for k in g0}
     worst = max(errs, key=errs.get)
     emb = model.representation.pair_embedding
-    fused_emb = float(getattr(emb, "_fused_bw", (None, None))[1] is not None)      # the embedding TP's gradients took the fused kernel + adjoint program (num_types 24 = 2 x 12 channels)
+    fused_emb = float(emb._fused_bw is not None and emb._fused_bw[1] is not None)      # the embedding TP's gradients took the fused kernel + adjoint program (num_types 24 = 2 x 12 channels)
     return {"embedding_fused_route": fused_emb, "loss_rel_err": float((l1 - l0).abs() / l0.abs()), "grad_max_rel_err": errs[worst], "worst": worst, "n_params": len(g0), "fused_route": float(sizes[0][0] > 0),
             "first_conv_wgrad_mfma_ratio": (sizes[0][0] / sizes[1][0]) if sizes[1][0] else 1.0, "first_conv_adjoint_mfma_ratio": sizes[0][1] / sizes[1][1]}
 

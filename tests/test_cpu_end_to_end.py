@@ -97,6 +97,39 @@ def test_device_repack_equals_recompile_on_cpu(cpu_backend):
     assert r["inference_rel_diff"] < 1e-6 and r["step_moved_H"] > 1e-3, r      # validate -> step -> validate uses the new weights (stale ResidualBlock row program)
 
 
+@pytest.mark.parametrize("transformer", [False, True], ids=["conv", "transformer"])
+def test_device_repack_equals_recompile_every_program_kind(cpu_backend, transformer):
+    """64-wide radial layers, num_types 24: the fused weight-gradient route, so that the stepped model holds EVERY kind of uploaded program of a
+    MessagePackBlock when its weights move -- a kind that refresh() forgot trains on stale weights (without the fused tables: grad_max_rel_diff 0.19).
+    The presence of each kind is asserted: a change that stops building one must not turn this case into a no-op."""
+    r = G.check_refresh_equals_recompile(device="cpu", transformer=transformer, radial=(16, 64), num_types=24)
+    assert all(r["kinds"].get(k, 0) >= 1 for k in G.MESSAGE_PACK_PROGRAM_KINDS) and r["embedding_fused_route"], r
+    assert r["packers"] >= 8 and r["loss_rel_diff"] < 1e-6 and r["grad_max_rel_diff"] < 1e-5, r
+    assert r["inference_rel_diff"] < 1e-6 and r["step_moved_H"] > 1e-3, r
+
+
+def test_merged_compile_falls_back_whole_when_the_reduced_program_does_not_fit(monkeypatch):
+    """a block compiled with merged row tiles whose REDUCED program does not fit the input-stationary kernel (after the complete one uploaded) falls back to the
+    plain programs as a whole: nothing merged stays in the table, the recorded merge groups are empty (so no plain twins, and refresh() tags what is uploaded)"""
+    from hamgnn_amd import nn as hnn, ops
+    m = hnn.MessagePackBlock(G.MINI, G.MINI, G.SH, G.MINI, 8, [16, 16]).set_structural_zeros(node=(1,), edge=(1,))
+    real, calls = ops.DeviceProgram, []
+
+    def upload(prog, device, schedule="seg"):
+        calls.append((schedule, bool(prog.vsegs)))
+        if len(calls) == 2:
+            raise NotImplementedError
+        return real(prog, device, schedule)
+    monkeypatch.setattr(ops, "DeviceProgram", upload)
+    m.compile(torch.device("cpu"), unrotate=False)
+    assert calls[:2] == [("is", True), ("is", True)] and not any(merged for _, merged in calls[2:]), calls      # (merged complete, merged reduced: refused; then plain)
+    held = m.programs()
+    assert set(held) == {("forward", False, False), ("forward", True, False)} and m._dp is held[("forward", False, False)]
+    assert not m._groups and not m._groups_z and not any(dp.prog.vsegs for dp in held.values())
+    assert all(e.tag[3] is False for e in m._programs.values())
+    assert m._dp_for(16, True) is held[("forward", True, False)] and m._dp_for(16) is m._dp      # a split launch: no twin is built
+
+
 def test_device_repack_equals_recompile_attention_backbone(cpu_backend):
     r = G.check_refresh_equals_recompile(device="cpu", transformer=True)
     assert r["packers"] >= 8 and r["loss_rel_diff"] < 1e-6 and r["grad_max_rel_diff"] < 1e-5, r

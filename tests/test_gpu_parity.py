@@ -347,10 +347,14 @@ def test_full_model_backward_default_irreps():
     assert r["loss_rel_err"] < G.TOL and r["max_rel_err"] < G.TOL, r
 
 
-@pytest.mark.parametrize("legacy", [False, True])
-def test_device_repack_equals_recompile(legacy):
-    r = G.check_refresh_equals_recompile(legacy=legacy)
+@pytest.mark.parametrize("kw", [dict(legacy=False), dict(legacy=True), dict(radial=(16, 64), num_types=24), dict(radial=(16, 64), num_types=24, transformer=True)],
+                         ids=["False", "True", "every_program_kind", "every_program_kind_transformer"])
+def test_device_repack_equals_recompile(kw):
+    """every_program_kind: the fused weight-gradient route -- the stepped model holds every kind of uploaded program of a MessagePackBlock when its weights move"""
+    r = G.check_refresh_equals_recompile(**kw)
     print(r)
+    if "radial" in kw:
+        assert all(r["kinds"].get(k, 0) >= 1 for k in G.MESSAGE_PACK_PROGRAM_KINDS) and r["embedding_fused_route"], r
     # (device repack: hg_block_gemm forms the L' products in fp64 in its own order, one fp64 ulp from the host's BLAS -> fp32 weights that may differ in the last bit)
     assert r["packers"] >= 8 and r["loss_rel_diff"] < G.SAME_MATH_TOL and r["grad_max_rel_diff"] < G.TOL, r
     assert r["inference_rel_diff"] < G.SAME_MATH_TOL and r["step_moved_H"] > 1e-3, r      # inference -> step -> inference: no stale cached chain
