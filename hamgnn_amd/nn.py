@@ -1284,14 +1284,16 @@ class _ProductBasis(nn.Module):
 
 
 class CorrProductBlock(nn.Module):
-    """Drop-in for hamgnn/nn/interaction_blocks.py:168-260 (correlation 1, 2 -- the reference default -- or 3): linear_pre -> symmetric
+    """Drop-in for hamgnn/nn/interaction_blocks.py:168-260 (correlation 1, 2 -- the reference default --, 3 or 4): linear_pre -> symmetric
     contraction with element-dependent weights -> prod.linear -> linear_out (+ linear_sc skip), all on planar node rows; same parameter
-    names.  The nu <= 2 part of the contraction is the hg_sym_contraction kernel, the nu = 3 term hg_sym_contraction3 (backward: hamgnn_amd/corr3.py)."""
+    names.  The nu <= 2 part of the contraction is the hg_sym_contraction kernel, the nu = 3 term hg_sym_contraction3 (backward: hamgnn_amd/corr3.py),
+    the nu = 4 term and its adjoint the order-generic kernels of csrc/sym_contraction_nu.hip.  HG_CORR_KERNEL=nu in the environment sends EVERY
+    term, forward and adjoint, through the generic kernels (opt-in; unset, correlation <= 3 launches what it always launched)."""
 
     def __init__(self, irreps_node_feats, num_hidden_features, correlation, num_elements, use_skip_connections=True):
         super().__init__()
-        if correlation not in (1, 2, 3):
-            raise NotImplementedError("CorrProductBlock: correlation 1, 2 (the reference default) and 3 are built")
+        if correlation not in (1, 2, 3, 4):
+            raise NotImplementedError("CorrProductBlock: correlation 1, 2 (the reference default), 3 and 4 are built")
         self.correlation = correlation
         self.irreps = Irreps(irreps_node_feats)
         if len({(l, p) for _, l, p in self.irreps}) != len(self.irreps):
@@ -1318,13 +1320,37 @@ class CorrProductBlock(nn.Module):
         # correlation 1: the kernel's nu = 2 loop runs over empty entry lists; it still wants a weight pointer
         self._W2 = cat(2) if self.correlation >= 2 else torch.zeros(self._W1.shape[0], 1, self._W1.shape[2], device=device)
         self._W3 = cat(3) if self.correlation >= 3 else None
+        self._W4 = cat(4) if self.correlation >= 4 else None
         self._hdim = P.PlanarLayout(self.irreps_hidden).dim
         return self
 
-    def _contract(self, h, zi, W1, W2, W3):
+    @staticmethod
+    def _generic_kernels():
+        """HG_CORR_KERNEL=nu: every term of the contraction on the order-generic kernels (read per call: a test or an A/B run flips it)"""
+        v = os.environ.get("HG_CORR_KERNEL", "")
+        if v not in ("", "nu"):
+            raise ValueError(f"HG_CORR_KERNEL={v!r}: the only value is 'nu'")
+        return v == "nu"
+
+    def _adjoint_tab(self, nu):
+        """the nu-th entry list transposed by component and by kappa (plan.sym_contraction_adjoint_tables), uploaded once per device"""
+        if f"entH{nu}" not in self._tab:
+            dev = self._tab["ell_off"].device
+            for k, v in P.sym_contraction_adjoint_tables(self._tab_np, nu).items():
+                self._tab[f"{k}{nu}"] = torch.from_numpy(v).to(dev)
+        return self._tab
+
+    def _contract(self, h, zi, W1, W2, W3, W4=None):
+        if self._generic_kernels():
+            c = torch.zeros(h.shape[0], self._hdim, device=h.device, dtype=torch.float32)       # channel padding stays zero
+            for nu, W in enumerate((W1, W2, W3, W4)[:self.correlation], start=1):
+                c = ops.sym_contraction_nu(nu, h, zi, self.num_hidden, self._tab, W, c)
+            return c
         c = ops.sym_contraction(h, zi, self.num_hidden, self._tab, W1, W2, self._hdim)
         if W3 is not None:                                     # correlation 3: its own kernel adds the nu = 3 term onto the same rows
             c = ops.sym_contraction3(h, zi, self.num_hidden, self._tab, W3, c)
+        if W4 is not None:                                     # correlation 4: the order-generic kernel adds the nu = 4 term
+            c = ops.sym_contraction_nu(4, h, zi, self.num_hidden, self._tab, W4, c)
         return c
 
     MIX_BYTES = 256 << 20          # per-node weight mixtures held at once (charge doping): [chunk, K_nu, C] floats over all nu
@@ -1332,42 +1358,52 @@ class CorrProductBlock(nn.Module):
     def _mix_chunks(self, N):
         """node ranges whose per-node weight mixtures W[z_n] + delta_n @ W (all nu) stay below MIX_BYTES: with correlation 3 a node's blocks reach
         thousands of K x C floats, so N x that -- several times over in the backward -- is what an un-chunked pass would allocate"""
-        per = 4 * sum(int(W[0].numel()) for W in (self._W1, self._W2, self._W3) if W is not None)
+        per = 4 * sum(int(W[0].numel()) for W in (self._W1, self._W2, self._W3, self._W4) if W is not None)
         step = max(64, int(self.MIX_BYTES // max(per, 1)))
         return [(a, min(N, a + step)) for a in range(0, N, step)]
 
     def _mixed(self, z, delta):
         """apply_charge_doping: the reference contracts the element weights with node_attrs = one_hot(z) + delta (interaction_blocks.py:251,
         symmetric_contraction.py einsum '...,ek'), i.e. every node gets its own mixture of the element blocks: W_eff[n] = W[z_n] + delta_n @ W.
-        Returns (attrs [N, T], per-node weights of nu = 1, 2, 3, node index as the 'element' index) for the same kernel.  Callers pass node CHUNKS."""
+        Returns (attrs [N, T], per-node weights of nu = 1, 2, 3, 4, node index as the 'element' index) for the same kernel.  Callers pass node CHUNKS."""
         T = self._W1.shape[0]
         A = torch.nn.functional.one_hot(z.long(), T).to(self._W1.dtype) + delta.to(self._W1.dtype)
         mix = lambda W: None if W is None else (A @ W.reshape(T, -1)).reshape(-1, *W.shape[1:]).contiguous()
-        return A, mix(self._W1), mix(self._W2), mix(self._W3), torch.arange(z.shape[0], device=z.device, dtype=z.dtype)
+        return A, mix(self._W1), mix(self._W2), mix(self._W3), mix(self._W4), torch.arange(z.shape[0], device=z.device, dtype=z.dtype)
 
     def _contract_doped(self, h, z, delta):
         out = []
         for a, b in self._mix_chunks(int(z.shape[0])):
-            _, W1, W2, W3, zi = self._mixed(z[a:b], delta[a:b])
-            out.append(self._contract(h[a:b].contiguous(), zi, W1, W2, W3))
+            _, W1, W2, W3, W4, zi = self._mixed(z[a:b], delta[a:b])
+            out.append(self._contract(h[a:b].contiguous(), zi, W1, W2, W3, W4))
         return out[0] if len(out) == 1 else torch.cat(out, 0)
 
     def backward(self, node_planar, z, g_out, delta=None):
         """gradient of forward(node, z) for the gradient g_out of the rows it returned: (g_node, {parameter name: gradient}).
-        Linears: streaming-kernel adjoints + GEMM weight gradients; the symmetric contraction: hamgnn_amd/backward_corr.py.
+        Linears: streaming-kernel adjoints + GEMM weight gradients; the symmetric contraction: hamgnn_amd/backward_corr.py (nu <= 2),
+        hamgnn_amd/corr3.py (nu = 3) and hg_sym_contraction_nu_backward (nu = 4; every nu under HG_CORR_KERNEL=nu).
         With the charge-doping correction `delta` the gradient with respect to it comes back under the key "_g_delta"."""
         from .backward_corr import sym_contraction_backward
         if self._tab is None:
             self.compile(node_planar.device)
         h = self.linear_pre(node_planar)
-        c = self._contract(h, z, self._W1, self._W2, self._W3) if delta is None else self._contract_doped(h, z, delta)
+        c = self._contract(h, z, self._W1, self._W2, self._W3, self._W4) if delta is None else self._contract_doped(h, z, delta)
         p = self.prod.linear(c)
         grads = {"linear_out.weight": self.linear_out.weight_grad(p, g_out), }
         g_p = self.linear_out.backward_data(g_out)
         grads["prod.linear.weight"] = self.prod.linear.weight_grad(c, g_p)
         g_c = self.prod.linear.backward_data(g_p)
 
-        def contraction_grads(hc, zi, W1, W2, W3, gc, per_node):
+        generic = self._generic_kernels()
+
+        def adjoint_nu(nu, hc, zi, W, gc, g_h_, per_node):
+            """the HIP adjoint of one term: its g_h is added onto g_h_ in place, its g_W returned"""
+            return ops.sym_contraction_nu_backward(nu, hc, zi, self.num_hidden, self._adjoint_tab(nu), W, gc, g_h_, per_node=per_node)
+
+        def contraction_grads(hc, zi, W1, W2, W3, W4, gc, per_node):
+            if generic:
+                g_h_ = torch.zeros(tuple(hc.shape), device=hc.device, dtype=hc.dtype)
+                return g_h_, [adjoint_nu(nu, hc, zi, W, gc, g_h_, per_node) for nu, W in enumerate((W1, W2, W3, W4)[:self.correlation], start=1)]
             g_h_, gW1, gW2 = sym_contraction_backward(self._tab, hc, zi, W1, W2, self.num_hidden, gc, per_node=per_node)
             gW_ = [gW1, gW2]
             if W3 is not None:
@@ -1375,17 +1411,20 @@ class CorrProductBlock(nn.Module):
                 g_h3, gW3 = sym3_backward(self._tab, hc, zi, W3, self.num_hidden, gc, per_node=per_node)
                 g_h_ = g_h_ + g_h3
                 gW_.append(gW3)
+            if W4 is not None:
+                g_h_ = g_h_.contiguous()
+                gW_.append(adjoint_nu(4, hc, zi, W4, gc, g_h_, per_node))
             return g_h_, gW_[:self.correlation]
 
         if delta is None:
-            g_h, gW = contraction_grads(h, z, self._W1, self._W2, self._W3, g_c, False)
+            g_h, gW = contraction_grads(h, z, self._W1, self._W2, self._W3, self._W4, g_c, False)
         else:                                                  # per-node gradients back onto the element blocks and onto the attributes, chunk by chunk
             T = self._W1.shape[0]
-            Wel = [self._W1, self._W2, self._W3][:self.correlation]
+            Wel = [self._W1, self._W2, self._W3, self._W4][:self.correlation]
             g_h_parts, g_delta_parts, gW = [], [], [torch.zeros_like(W) for W in Wel]
             for a, b in self._mix_chunks(int(z.shape[0])):
-                A, W1, W2, W3, zi = self._mixed(z[a:b], delta[a:b])
-                g_h_c, gW_c = contraction_grads(h[a:b].contiguous(), zi, W1, W2, W3, g_c[a:b].contiguous(), True)
+                A, W1, W2, W3, W4, zi = self._mixed(z[a:b], delta[a:b])
+                g_h_c, gW_c = contraction_grads(h[a:b].contiguous(), zi, W1, W2, W3, W4, g_c[a:b].contiguous(), True)
                 flat = [g.reshape(g.shape[0], -1) for g in gW_c]
                 g_h_parts.append(g_h_c)
                 g_delta_parts.append(sum(f @ W.reshape(T, -1).t() for f, W in zip(flat, Wel)))
@@ -1417,6 +1456,6 @@ class CorrProductBlock(nn.Module):
         if delta is not None:
             c = self._contract_doped(h, z, delta)
         else:
-            c = self._contract(h, z, self._W1, self._W2, self._W3)
+            c = self._contract(h, z, self._W1, self._W2, self._W3, self._W4)
         skip = [self.linear_sc(node_planar)] if self.use_skip_connections else []
         return self.linear_out(self.prod.linear(c), res=skip)

@@ -929,6 +929,70 @@ def sym_contraction3(h, z, C, tab, W3, out):
 
 
 @_on_tensor_device
+def sym_contraction_nu(nu, h, z, C, tab, W, out):
+    """adds the term of order nu (1 ... 4) of the symmetric contraction to the rows `out` (in place; csrc/sym_contraction_nu.hip): the nu = 4 term of a
+    `correlation: 4` block onto what sym_contraction / sym_contraction3 wrote, or every term onto zeros (HG_CORR_KERNEL=nu)"""
+    _require_gpu(h)
+    h = h.contiguous()
+    check(lib().hg_sym_contraction_nu(i32(nu), ptr(h), i64(h.stride(0)), ptr(z), i64(h.shape[0]), i32(C), i32(tab["num_ell"]), ptr(tab["ell_off"]),
+                                      i32(tab["nout"]), ptr(tab["out_off"]), ptr(tab[f"ptr{nu}"]), ptr(tab[f"ent{nu}"]), ptr(W), i32(W.shape[1]), ptr(out),
+                                      i64(out.stride(0)), _stream()), "hg_sym_contraction_nu")
+    return out
+
+
+SYM_NU_RUN = 32        # nodes of one element a lane of the weight-gradient kernel walks; the runs of an element are added in order afterwards
+
+
+def _element_runs(z, T, run):
+    """nodes sorted by element (stably: index order inside an element) and cut into runs of at most `run` nodes of ONE element, without a host
+    sync: (run_ptr int32[G + 1], nodes int32[N], element of every run int64[G], G) with G = ceil(N / run) + T >= the runs in use (the rest are empty)"""
+    N, dev = int(z.shape[0]), z.device
+    zl = z.long()
+    order = torch.sort(zl, stable=True).indices
+    zs = zl[order]
+    counts = torch.bincount(zl, minlength=T)
+    if counts.shape[0] != T:
+        raise IndexError(f"sym_contraction_nu_backward: an element index beyond the {T} weight blocks")
+    nrun = (counts + run - 1) // run
+    run_end = torch.cumsum(nrun, 0)
+    rank = torch.arange(N, device=dev) - (torch.cumsum(counts, 0) - counts)[zs]
+    G = (N + run - 1) // run + T
+    gid = (run_end - nrun)[zs] + rank // run
+    run_ptr = torch.zeros(G + 1, device=dev, dtype=torch.int64)
+    run_ptr[1:] = torch.cumsum(torch.bincount(gid, minlength=G), 0)
+    elem = torch.searchsorted(run_end, torch.arange(G, device=dev), right=True).clamp_(max=T - 1)
+    return run_ptr.to(torch.int32), order.to(torch.int32), elem, G
+
+
+@_on_tensor_device
+def sym_contraction_nu_backward(nu, h, z, C, tab, W, g_out, g_h, per_node=False):
+    """adjoint of the term of order nu (hg_sym_contraction_nu_backward): the gradient with respect to the hidden rows is ADDED onto g_h [N, Dp] in
+    place, the gradient with respect to W [T, K, C] returned.  tab holds the transposed tables ptrH{nu} / entH{nu} / ptrW{nu} / entW{nu}
+    (plan.sym_contraction_adjoint_tables).  per_node: one weight block per node (z = arange(N), charge doping) -> one gradient block per node.
+    Otherwise a lane sums a run of SYM_NU_RUN nodes of one element in index order and the runs of an element are added in order
+    (scatter_rows: a fixed order, no atomics)."""
+    _require_gpu(h)
+    h, g_out = h.contiguous(), g_out.contiguous()
+    N, T, K = int(h.shape[0]), int(W.shape[0]), int(W.shape[1])
+    if N == 0:
+        return torch.zeros_like(W)
+    if per_node:
+        assert T == N, "per-node weights: one block per node"
+        run_ptr = nodes = elem = None
+        G = N
+    else:
+        run_ptr, nodes, elem, G = _element_runs(z, T, SYM_NU_RUN)
+    gW = torch.empty(G, K, C, device=h.device, dtype=torch.float32)
+    check(lib().hg_sym_contraction_nu_backward(i32(nu), ptr(h), i64(h.stride(0)), ptr(g_out), i64(g_out.stride(0)), ptr(z), i64(N), i32(C),
+                                               i32(tab["num_ell"]), ptr(tab["ell_off"]), i32(tab["nout"]), ptr(tab["out_off"]), ptr(tab[f"ptrH{nu}"]),
+                                               ptr(tab[f"entH{nu}"]), ptr(tab[f"ptrW{nu}"]), ptr(tab[f"entW{nu}"]), ptr(W), i32(K), i64(G), ptr(run_ptr),
+                                               ptr(nodes), ptr(g_h), i64(g_h.stride(0)), ptr(gW), _stream()), "hg_sym_contraction_nu_backward")
+    if per_node:
+        return gW
+    return scatter_rows(elem, gW.reshape(G, K * C), T, persistent=False).reshape(T, K, C)
+
+
+@_on_tensor_device
 def sym_contraction(h, z, C, tab, W1, W2, out_dim):
     """tab: device tensors of plan.sym_contraction_tables; W1 [nel, K1, C], W2 [nel, K2, C]; returns planar hidden rows [N, out_dim]"""
     _require_gpu(h)

@@ -630,7 +630,7 @@ def corr_hidden_irreps(irreps_node, num_hidden) -> Irreps:
 
 
 def sym_contraction_tables(irreps_hidden: Irreps, correlation: int = 2):
-    """Sparse coupling tables of the MACE symmetric contraction with correlation <= 3 on `num_hidden x irreps`
+    """Sparse coupling tables of the MACE symmetric contraction with correlation <= 4 on `num_hidden x irreps`
     (hamgnn/toolbox/mace/tools/cg.py:16-131 U_matrix_real, modules/symmetric_contraction.py:101-233):
         out_k[c, w] = sum_x ( sum_kap U1_k[w, x, kap] W1_k[z, kap, c]
                               + sum_i ( sum_kap U2_k[w, x, i, kap] W2_k[z, kap, c]
@@ -644,8 +644,10 @@ def sym_contraction_tables(irreps_hidden: Irreps, correlation: int = 2):
     Returns dict(ell_off, out_off, ptr1, ent1, ptr2, ent2, K1, K2 (per target), num_ell, nout [, ptr3, ent3, K3]) with
       ell_off[i]  planar offset of ell component i (channel 0) in the hidden layout,   out_off[o] same for output element o = (k, w)
       ent1 rows (x, kappa_global, value-bits), ent2 rows (x, i, kappa_global, value-bits), ent3 rows (x, i, j, kappa_global, value-bits);
-      kappa_global indexes the concatenated weights of all targets.  ent1 / ent2 feed hg_sym_contraction, ent3 hamgnn_amd/corr3.py."""
-    assert correlation in (1, 2, 3), "correlation > 3 is not built"
+      kappa_global indexes the concatenated weights of all targets.  ent1 / ent2 feed hg_sym_contraction, ent3 hamgnn_amd/corr3.py.
+    correlation 4 adds ptr4, ent4 rows (x, i, j, l, kappa_global, value-bits) and K4 (_sym4_tables; csrc/sym_contraction_nu.hip); everything
+    listed above is then what correlation 3 returns."""
+    assert correlation in (1, 2, 3, 4), "correlation > 4 is not built"
     lay = PlanarLayout(irreps_hidden)
     irs = [(l, p) for _, l, p in irreps_hidden]
     sl, o = [], 0
@@ -708,4 +710,99 @@ def sym_contraction_tables(irreps_hidden: Irreps, correlation: int = 2):
                ptr2=np.asarray(ptr2, np.int32), ent2=pack(ent2, 3), K1=K1, K2=K2, num_ell=num_ell, nout=len(out_off))
     if correlation >= 3:
         tab.update(ptr3=np.asarray(ptr3, np.int32), ent3=pack(ent3, 4, 5), K3=K3)
+    if correlation >= 4:
+        ptr4, ent4, K4 = _sym4_tables(irs, sl)
+        tab.update(ptr4=ptr4, ent4=ent4, K4=K4)
     return tab
+
+
+# nu = 4 entries a planner call may return.  The U_4 list grows with about the fourth power of the component count: 32 625 entries for
+# 4x0e+3x1o+2x2e (9 components), 981 692 for 4x0e+2x1o+2x2e+2x3o (16 components).  An entry costs 24 B in ent4 and 5 x 24 B in the two
+# transposed tables of the adjoint, so 2^20 entries are 151 MB of device tables -- the largest measured shape fits, the next l does not.
+SYM4_ENTRY_CAP = 1 << 20
+
+# Intermediate irreps the nu = 4 couplings may pass through.  The reference hard-codes this list for correlation 4 and no other order (U_matrix_real,
+# cg.py:99-114 `filter_ir_mid`): natural parity (l, (-1)^l) only, applied to the result of EVERY coupling step, the target included -- 46 / 76 / 85 paths
+# instead of 55 / 124 / 148 for 4x0e+3x1o+2x2e, and its weights_max has that many rows, so a checkpoint only loads with the same list.  A target irrep
+# outside the list has no path at all (the reference fails on it); the planner refuses it.  None = no filter: the plain enumeration of wigner_nj that
+# oracle/mace_ref.py restates for every order (the oracle comparisons of the test suite set this).
+SYM4_FILTER_IR_MID = tuple((l, (-1) ** l) for l in range(12))
+
+
+def _sym4_tables(irs, sl):
+    """nu = 4 part of sym_contraction_tables.  Paths in the order wigner_nj([irreps] * 4) returns them (cg.py:46-87): the (a, b) pairs coupled to
+    every intermediate irrep and stably sorted by it, each with a third factor c coupled to every intermediate irrep and again stably sorted by
+    it, then the fourth factor d, every coupling result held to SYM4_FILTER_IR_MID;  C = sum_{m2, m3} sqrt(2 l2 + 1) w3j(l2, l_a, l_b)[m2] sqrt(2 l3 + 1) w3j(l3, l2, l_c)[m3, m2] sqrt(2L + 1)
+    w3j(L, l3, l_d)[., m3, .].  Returns (ptr4 int32[nout + 1], ent4 int32[., 6], K4 per target); more than SYM4_ENTRY_CAP entries raise."""
+    n = len(irs)
+    keep = (lambda ir: True) if SYM4_FILTER_IR_MID is None else (lambda ir, allowed=frozenset(SYM4_FILTER_IR_MID): ir in allowed)
+    missing = [ir for ir in irs if not keep(ir)]
+    if missing:
+        raise NotImplementedError(f"sym_contraction_tables: correlation 4 reaches no target of unnatural parity (irreps {missing}): the reference "
+                                  "filters every nu = 4 coupling to the irreps (l, (-1)^l) and cannot build this block either")
+    ok = lambda l1, l2, l3: abs(l1 - l2) <= l3 <= l1 + l2
+    w3 = lambda l1, l2, l3: math.sqrt(2 * l1 + 1) * so3.wigner_3j(l1, l2, l3)
+    left2 = [((lm, irs[a][1] * irs[b][1]), a, b) for a in range(n) for b in range(n)
+             for lm in range(abs(irs[a][0] - irs[b][0]), irs[a][0] + irs[b][0] + 1) if keep((lm, irs[a][1] * irs[b][1]))]
+    left2.sort(key=lambda t: t[0])                              # (list.sort is stable)
+    left3 = [((l3, m2[1] * irs[c][1]), i2, c) for i2, (m2, a, b) in enumerate(left2) for c in range(n)
+             for l3 in range(abs(m2[0] - irs[c][0]), m2[0] + irs[c][0] + 1) if keep((l3, m2[1] * irs[c][1]))]
+    left3.sort(key=lambda t: t[0])
+    c3_cache = {}
+
+    def c3(i3):                                                 # [m3, a, b, c]
+        if i3 not in c3_cache:
+            (l3, _), i2, c = left3[i3]
+            (l2, _), a, b = left2[i2]
+            c3_cache[i3] = np.einsum("mab,nmc->nabc", w3(l2, irs[a][0], irs[b][0]), w3(l3, l2, irs[c][0]))
+        return c3_cache[i3]
+    rows, counts, K4, kg, total = [], [], [], 0, 0
+    for (L, pL) in irs:
+        paths = [(i3, d) for i3, (m3, _, _) in enumerate(left3) for d in range(n) if m3[1] * irs[d][1] == pL and ok(m3[0], irs[d][0], L)]
+        cols = []
+        for kap, (i3, d) in enumerate(paths):
+            (l3, _), i2, c = left3[i3]
+            _, a, b = left2[i2]
+            C = np.einsum("nabc,wnd->wabcd", c3(i3), w3(L, l3, irs[d][0]))
+            nz = np.nonzero(np.abs(C) > 1e-14)
+            if nz[0].size:
+                cols.append(np.stack([nz[0], sl[a][0] + nz[1], sl[b][0] + nz[2], sl[c][0] + nz[3], sl[d][0] + nz[4],
+                                      np.full(nz[0].size, kg + kap), C[nz].astype(np.float32).view(np.int32)], axis=1))
+                total += int(nz[0].size)
+                if total > SYM4_ENTRY_CAP:
+                    raise NotImplementedError(f"sym_contraction_tables: the nu = 4 table of these irreps has at least {total} entries, "
+                                              f"more than the {SYM4_ENTRY_CAP} a correlation-4 block is built for")
+        E = np.concatenate(cols, 0) if cols else np.zeros((0, 7), np.int64)
+        E = E[np.argsort(E[:, 0], kind="stable")]                # rows per component w of the target, paths in order inside a row
+        rows.append(E[:, 1:])
+        counts.append(np.bincount(E[:, 0], minlength=2 * L + 1))
+        K4.append(len(paths))
+        kg += len(paths)
+    ent4 = np.concatenate(rows, 0).astype(np.int32)
+    if ent4.shape[0] == 0:
+        ent4 = np.zeros((1, 6), np.int32)
+    ptr4 = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int32)
+    return ptr4, np.ascontiguousarray(ent4), K4
+
+
+def sym_contraction_adjoint_tables(tab, nu: int):
+    """The nu-th entry list of sym_contraction_tables transposed twice for hg_sym_contraction_nu_backward (csrc/sym_contraction_nu.hip):
+      ptrH int32[num_ell + 1], entH int32[., nu + 2]  by component: for every (entry, position t) whose position reads the component, in (entry, t)
+                                                      order, {output element o, the other nu - 1 components, kappa, value-bits}
+      ptrW int32[K + 1],       entW int32[., nu + 2]  by kappa, entries in order: {planar offset of o, planar offsets of the nu components, value-bits}
+    (K = the concatenated path count of order nu)."""
+    ptr, ent = np.asarray(tab[f"ptr{nu}"]), np.asarray(tab[f"ent{nu}"])
+    E, K = int(ptr[-1]), int(sum(tab[f"K{nu}"]))
+    ent = ent[:E]
+    o = np.repeat(np.arange(len(ptr) - 1, dtype=np.int32), np.diff(ptr))
+    idx, kap, val = ent[:, :nu], ent[:, nu], ent[:, -1]
+    comp = idx.reshape(-1)                                      # (entry, t) order
+    others = np.stack([np.delete(idx, t, axis=1) for t in range(nu)], axis=1).reshape(E * nu, nu - 1)
+    H = np.concatenate([np.repeat(o, nu)[:, None], others, np.repeat(kap, nu)[:, None], np.repeat(val, nu)[:, None]], axis=1).astype(np.int32)
+    order = np.argsort(comp, kind="stable")
+    ptrH = np.concatenate([[0], np.cumsum(np.bincount(comp, minlength=int(tab["num_ell"])))]).astype(np.int32)
+    Wt = np.concatenate([np.asarray(tab["out_off"])[o][:, None], np.asarray(tab["ell_off"])[idx], val[:, None]], axis=1).astype(np.int32)
+    korder = np.argsort(kap, kind="stable")
+    ptrW = np.concatenate([[0], np.cumsum(np.bincount(kap, minlength=K))]).astype(np.int32)
+    pad = lambda a: np.ascontiguousarray(a) if a.shape[0] else np.zeros((1, nu + 2), np.int32)
+    return dict(ptrH=ptrH, entH=pad(H[order]), ptrW=ptrW, entW=pad(Wt[korder]))

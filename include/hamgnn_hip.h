@@ -302,6 +302,28 @@ int hg_sym_contraction3(const float* h, int64_t h_stride, const int64_t* z, int6
                         int nout, const int32_t* out_off, const int32_t* ptr3, const int32_t* ent3, const float* W3, int K3,
                         float* out, int64_t out_stride, void* stream);
 
+/* One term of the same contraction, generic in the order nu = 1 ... 4 (csrc/sym_contraction_nu.hip), ADDED onto rows that exist:
+ *   out[o, c] += sum_{e in ent[o]} v_e W[z, kap_e, c] prod_{t < nu} h[c, i_{e,t}]
+ * ptr int32[nout + 1] / ent = the nu-th entry list of plan.sym_contraction_tables: rows of max(4, nu + 2) int32 {i_0 .. i_{nu-1}, kappa, .., value bits}
+ * (kappa in column nu, the value in the last column), W [num_elements][K][C].  A `correlation: 4` block adds its nu = 4 term with it; with
+ * HG_CORR_KERNEL=nu every term runs here.  One workgroup per node, a CSR row dealt to a fixed number of lanes whose partial sums are added in a
+ * fixed order: deterministic, no atomics.  Refuses (-2) hidden rows that do not fit 64 KB of LDS.                                          */
+int hg_sym_contraction_nu(int nu, const float* h, int64_t h_stride, const int64_t* z, int64_t N, int C, int num_ell, const int32_t* ell_off,
+                          int nout, const int32_t* out_off, const int32_t* ptr, const int32_t* ent, const float* W, int K, float* out,
+                          int64_t out_stride, void* stream);
+
+/* Adjoint of that term for the gradient g_out of the rows it added to (plan.sym_contraction_adjoint_tables gives the transposed tables):
+ *   g_h[n, i, c] += sum over every (entry, position) that reads component i   (ptrH int32[num_ell + 1], entH rows {o, the other nu - 1 components,
+ *                                                                               kappa, value bits}; g_h must hold what earlier terms gave, or 0)
+ *   g_W[g, kap, c] = sum over the nodes of group g, in list order, and the entries of kappa   (ptrW int32[K + 1], entW rows {planar offset of o,
+ *                                                                               planar offsets of the nu components, value bits}; every element written)
+ * Groups: grp_ptr int32[G + 1] into grp_idx int32[.] (node indices; e.g. the nodes of one element in index order), or grp_ptr = grp_idx = NULL and
+ * G = N: every node its own group (per-node weights, z = arange(N)).  g_W [G][K][C].  Both sums in a fixed order, no atomics.                */
+int hg_sym_contraction_nu_backward(int nu, const float* h, int64_t h_stride, const float* g_out, int64_t g_stride, const int64_t* z, int64_t N, int C,
+                                   int num_ell, const int32_t* ell_off, int nout, const int32_t* out_off, const int32_t* ptrH, const int32_t* entH,
+                                   const int32_t* ptrW, const int32_t* entW, const float* W, int K, int64_t G, const int32_t* grp_ptr,
+                                   const int32_t* grp_idx, float* g_h, int64_t gh_stride, float* g_W, void* stream);
+
 /* zero-point energy shift (hamgnn_output.py:3971-3981; SOC spin-diagonal real blocks :3892-3913), in place:
  *   dE = sum_{S>thr}(H - Href) / sum_{S>thr} S ;  H -= dE * S    -- one dE per call (= per batch, as the reference).
  * soc != 0: H/Href rows are (2 nao)^2, S rows nao^2; (uu+dd) differences, denominator 2 sum S, both diagonal blocks shifted.
