@@ -72,9 +72,6 @@ struct Prof { unsigned long long t[12]; unsigned long long last; };
 #define HG_T(k)
 #endif
 
-// ablation hooks (timing experiments only, tests/build_variants.sh): HG_SINK keeps a value alive without using it
-#define HG_SINK(v) asm volatile("" ::"v"(v))
-#define HG_LDA(p) (*(p))
 #ifndef HG_DMA_AUX
 #define HG_DMA_AUX 2              // cache policy of the B-operand DMA: nt (streamed once per CU; keeps the shared A lines in L1; r1 A/B: -3 %)
 #endif
@@ -168,9 +165,9 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
 #pragma unroll
             for (int G = 0; G < 4; ++G)
                 if (G0 + G < hgrp) {
-                    hb[G] = HG_LDA(reinterpret_cast<const f32x4*>(hrow + 16 * (G0 + G)));
+                    hb[G] = *reinterpret_cast<const f32x4*>(hrow + 16 * (G0 + G));
 #pragma unroll
-                    for (int rt = 0; rt < RTM; ++rt) wv[G][rt] = HG_LDA(w3 + ((G0 + G) * RTM + rt) * 64);
+                    for (int rt = 0; rt < RTM; ++rt) wv[G][rt] = w3[((G0 + G) * RTM + rt) * 64];
                 }
 #pragma unroll
             for (int G = 0; G < 4; ++G)
@@ -192,7 +189,7 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
 
     f32x4 av_n[RTM];
 #pragma unroll
-    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = HG_LDA(aw + rt * 64);
+    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = aw[rt * 64];
 #pragma unroll 1
     for (int si = 0; si < nsrc; ++si) {
         if (si >= nissued) {                                    // second source of a span pair too wide to share the ring
@@ -213,7 +210,7 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
                 for (int rt = 0; rt < RTM; ++rt) av[rt] = av_n[rt];
                 if (abase + G + 1 < nsrc * ngrp) {
 #pragma unroll
-                    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = HG_LDA(aw + ((abase + G + 1) * RTM + rt) * 64);
+                    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = aw[((abase + G + 1) * RTM + rt) * 64];
                 }
 #pragma unroll
                 for (int c = 0; c < NC; ++c) bv[c] = *reinterpret_cast<const f32x4*>(fb + (c * cdir + 4 * G) * 64);
@@ -234,7 +231,7 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
                 for (int rt = 0; rt < RTM; ++rt) av[rt] = av_n[rt];
                 if (abase + G + 1 < nsrc * ngrp) {
 #pragma unroll
-                    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = HG_LDA(aw + ((abase + G + 1) * RTM + rt) * 64);
+                    for (int rt = 0; rt < RTM; ++rt) av_n[rt] = aw[((abase + G + 1) * RTM + rt) * 64];
                 }
                 const int nq = ksteps - 4 * G;                 // K-steps in this group (>= 4 except in the tail group)
 #pragma unroll
@@ -261,11 +258,11 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
         {
         f32x4 a2_n[RTM];
 #pragma unroll
-        for (int rt = 0; rt < RTM; ++rt) a2_n[rt] = HG_LDA(a2 + rt * 64);
+        for (int rt = 0; rt < RTM; ++rt) a2_n[rt] = a2[rt * 64];
 #pragma unroll
         for (int rt = 0; rt < RTM; ++rt)
 #pragma unroll
-            for (int c = 0; c < NC; ++c) mid[rt][c] = mid[rt][c] * S[rt] * HG_LDA(cf + (rt * NC + c) * 4);
+            for (int c = 0; c < NC; ++c) mid[rt][c] = mid[rt][c] * S[rt] * cf[(rt * NC + c) * 4];
 
         HG_T(4);                                                // mid *= S * cf (+ a2 / cf loads)
         // ------------------------------------------------------------ GEMM2: tile[w'', m] += L' fragments x mid
@@ -277,7 +274,7 @@ __device__ __forceinline__ void item_body(const TpArgs& A, const float* __restri
             for (int rt = 0; rt < RTM; ++rt) av[rt] = a2_n[rt];
             if (rtp + 1 < rto) {
 #pragma unroll
-                for (int rt = 0; rt < RTM; ++rt) a2_n[rt] = HG_LDA(a2 + ((rtp + 1) * RTM + rt) * 64);
+                for (int rt = 0; rt < RTM; ++rt) a2_n[rt] = a2[((rtp + 1) * RTM + rt) * 64];
             }
             // rows beyond mul_k (fragment padding) are redirected to a trash row behind the tile: no divergent branches
             float* __restrict__ trow[4];

@@ -143,12 +143,8 @@ __device__ __forceinline__ void wg_idle(const WgArgs& A, const int* __restrict__
 
 // Every LDS operand of the MFMA phases has ONE consumer, and the scheduler emits read -> s_waitcnt lgkmcnt(0) -> v_mfma per operand: an LDS
 // round trip per MFMA, in all four waves of a workgroup at once (they run the phases in lock step).  WG_SGB(cond, n): "n LDS reads, then
-// n MFMAs" for the instructions just written (ISA audit, profiles/r03_wgrad.md); -DWG_NO_SGB restores the compiler's order.
-#ifndef WG_NO_SGB
+// n MFMAs" for the instructions just written (ISA audit, profiles/r03_wgrad.md).
 #define WG_SGB(cond, n) if (cond) { __builtin_amdgcn_sched_group_barrier(0x100, (n), 0); __builtin_amdgcn_sched_group_barrier(0x008, (n), 0); }
-#else
-#define WG_SGB(cond, n)
-#endif
 template <int NC, int NSRC, int G1, int G2>
 __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__ U, const int* __restrict__ Wr, const float* __restrict__ Wg,
                                         const int* __restrict__ chtab, float* __restrict__ lds, int split, int nsplit) {
@@ -197,21 +193,14 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
     __syncthreads();
 #pragma unroll 1
     for (int64_t it = R.it0; it < R.it1; ++it) {
-#ifdef WG_ABL_NOLOAD
-        const float* __restrict__ cur = lds;
-        float* __restrict__ nxt = lds + buf_floats;
-#else
         const float* __restrict__ cur = lds + ((it - R.it0) & 1) * buf_floats;
         float* __restrict__ nxt = lds + (((it - R.it0) & 1) ^ 1) * buf_floats;
-#endif
         const float* __restrict__ rowbase = cur + et * 16 * RS;
         const int64_t e_tile = (it * ET + et) * 16;
         const bool more = it + 1 < R.it1;
         // ---- the next iteration's rows start travelling: neither MFMA phase issues a load (the weights are resident), so they have the whole
         // iteration to land (vmcnt is in-order: any later load would have to wait for these)
-#if !defined(WG_ABL_NOLOAD) && !defined(WG_LATE_LOAD)
         if (more) wg_load(A, U, (it + 1) * ET * 16, st, tid);
-#endif
         f32x4 mid[NC], bm[NC];
         f32x4 sv = f32x4{0.f, 0.f, 0.f, 0.f};
         {
@@ -224,7 +213,6 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                 mid[c] = f32x4{0.f, 0.f, 0.f, 0.f};
                 bm[c] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-#ifndef WG_ABL_NOP1
 #pragma unroll
             for (int s = 0; s < NSRC; ++s) {
                 const float* __restrict__ xs = xa + (s ? xoff1 : 0) + xc0;
@@ -281,7 +269,6 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                 }
                 sv += sv2;
             }
-#endif
             if (NC == 1) {
                 mid[0] += mid2;
                 bm[0] += bm2;
@@ -299,9 +286,7 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
             for (int r = 0; r < 4; ++r) {
                 const int64_t e = e_tile + 4 * g + r;
                 const bool valid = e < A.rows;
-#ifndef WG_ABL_NOGS
                 if (valid && ch >= 0) gsp[e * gss + ch] = gsr[r];
-#endif
                 if (!valid) {
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
@@ -311,10 +296,6 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                 }
             }
         }
-#if !defined(WG_ABL_NOLOAD) && defined(WG_LATE_LOAD)
-        if (more) wg_load(A, U, (it + 1) * ET * 16, st, tid);
-#endif
-#ifndef WG_ABL_NOP2
         {
             // ---- phase 2: K = the 16 edges (K-step r: slot g <-> edge 4 g + r); A operand: lane (channel el, g) reads x[edge 4 g + r][channel]
             const float* __restrict__ xb = rowbase + (4 * g) * RS + el;
@@ -336,10 +317,7 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                 }
             }
         }
-#endif
-#ifndef WG_ABL_NOLOAD
         if (more) wg_store(U, nxt, st, tid);
-#endif
         __syncthreads();
     }
     // ---- accumulators: block (split, unit, wave), fragment f, [row][channel]: lane (row el, g) holds channels 4 g .. 4 g + 3
@@ -375,28 +353,14 @@ tp_wgrad_kernel(const WgArgs A, const int* __restrict__ units, const float* __re
     }
     const int nc = Wr[2], nsrc = U[0], g1 = U[12], g2 = (Wr[6] + 15) >> 4;
     switch (WG_CODE(nc, nsrc, g1, g2)) {
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 1
         WG_CASES_G4(1, 1, 1) WG_CASES_G4(1, 1, 2) WG_CASES_G4(1, 1, 3) WG_CASES_G4(1, 1, 4)
         WG_CASES_G4(1, 2, 1) WG_CASES_G4(1, 2, 2) WG_CASES_G4(1, 2, 3) WG_CASES_G4(1, 2, 4)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 3
         WG_CASES_MID(3)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 5
         WG_CASES_MID(5)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 7
         WG_CASES_MID(7)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 9
         WG_CASES_HI(9)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 11
         WG_CASES_HI(11)
-#endif
-#if !defined(WG_ONLY_NC) || WG_ONLY_NC == 13
         WG_CASES_HI(13)
-#endif
         default: wg_idle(A, U, lds, split, nsplit); break;     // (the planner never emits another shape)
     }
 }

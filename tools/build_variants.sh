@@ -1,7 +1,7 @@
 #!/bin/bash
 # builds kernel variants of libhamgnn_hip.so into hamgnn_amd/lib/variants/ for A/B timing on the GPU box:  name:"extra hipcc flags"
 # Only the files named in HG_VARIANT_FILES (default: tp_is) are recompiled with the flags; the other objects come from the regular build.
-#   tools/build_variants.sh base: cfp:"-DHG_CFP"        ->  hamgnn_amd/lib/variants/lib_base.so, lib_cfp.so  (select with HG_LIB_PATH)
+#   tools/build_variants.sh base: prof:"-DHG_PROF"      ->  hamgnn_amd/lib/variants/lib_base.so, lib_prof.so  (select with HG_LIB_PATH)
 set -e
 cd "$(dirname "$0")/../hamgnn_amd/csrc"
 make -j8 > /dev/null

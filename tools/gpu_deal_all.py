@@ -1,9 +1,8 @@
-"""Does the shipped edge kernel's result depend on how its waves line up?  (profiles/r06_tp_is.md section 7)
-Single-part launches CLAIM their work groups (atomic counter), so the four waves of a workgroup drift apart; the variant library `-DIS_DEAL_ALL` deals the same group table
-round-robin instead (group g0 + k NW + w to wave w): every wave starts an item at the same instant after each staging barrier -- the alignment under which the round's
-half-precision experiment failed in every forward.  A segment's items stay on one wave in table order either way, so the two builds must agree BIT FOR BIT.
-  python tools/gpu_deal_all.py save /tmp/h.pt          (default library)
-  HG_LIB_PATH=hamgnn_amd/lib/variants/lib_dealall.so python tools/gpu_deal_all.py check /tmp/h.pt [--forwards 30]"""
+"""Does a forward of the shipped library give the same bits in every replay and in another process?  (profiles/r06_tp_is.md sections 7 and 9; tools/gpu_split_validate.sh)
+`save` writes the Hamiltonian of one forward (and counts 5 replays against it); `check` runs the forward again, in a second process or under another HG_LIB_PATH, and counts the
+forwards that differ from the saved one by a bit.
+  python tools/gpu_deal_all.py save /tmp/h.pt
+  [HG_LIB_PATH=hamgnn_amd/lib/variants/lib_<name>.so] python tools/gpu_deal_all.py check /tmp/h.pt [--forwards 30]"""
 import argparse, os, sys, json
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
