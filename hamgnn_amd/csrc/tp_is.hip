@@ -34,6 +34,12 @@ struct ProfIs { unsigned long long t[12]; unsigned long long last; };
 // broadcast of lane q of every row of 16 lanes to that row: DPP row_newbcast (gfx90a+): lanes (g, *) <- lane (g, q).
 // x * (lane q of v's row of 16 lanes) in ONE VALU instruction: v_mul_f32 with the DPP control on its first source (the compiler keeps the
 // broadcast as a separate v_mov_b32_dpp: 2 000 of them in the default instantiation)
+// max(|a|, |b|, |c|) in one instruction
+__device__ __forceinline__ float is_absmax3(float a, float b, float c) {
+    float o;
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(o) : "v"(a), "v"(b), "v"(c));
+    return o;
+}
 #define IS_MB_CASE(Q) case Q: asm("v_mul_f32_dpp %0, %1, %2 row_newbcast:" #Q " row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v), "v"(x)); break;
 __device__ __forceinline__ float is_mul_bcast(float v, float x, int q) {
     float o;
@@ -102,6 +108,8 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
             // lo = f16((x 2^s - hi) 2^11);  S 2^(sw + sh) = W_hi h_hi + 2^-11 (W_hi h_lo + W_lo h_hi) -- 3 MFMAs of K = 32 per half of the 64 hidden units
             // = 6 x 16 pipe cycles per row tile where the fp32 form takes 16 x 32 (27.5 % of the launch's MFMAs), fp32 accumulation in two chains (the
             // half-precision MFMAs flush subnormal inputs: hence the scaled remainders), 22-bit operands (H moves by 6e-7 relative: profiles/r06_tp_is.md).
+            // sw is the program's (planner), sh the TILE's: chosen per phase from the 16 edges' rows where they are split (tp_is_kernel), so the rows may have any
+            // magnitude -- no half overflows, a unit is flushed only below 2^-26 of the tile's largest; hbr.c0 = 2^-(sw + sh) undoes both.
             // The weights' split twin follows the fp32 block: [t][rt][hi, lo][lane] float4 = 8 halves in the K-slot order of the resident rows.
             const f32x4* __restrict__ w3s = w3 + 4 * RTM * 64;
             f32x4 wh[2][RTM], wl[2][RTM], S1[RTM];
@@ -127,7 +135,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
                 for (int rt = 0; rt < RTM; ++rt) S1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wl[t][rt]), hbr.hi[t], S1[rt], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const float c0 = A.s_scale, c1 = A.s_scale * (1.f / 2048.f);
+            const float c0 = hbr.c0, c1 = hbr.c0 * (1.f / 2048.f);
 #pragma unroll
             for (int rt = 0; rt < RTM; ++rt) S[rt] = S[rt] * c0 + S1[rt] * c1;
         } else
@@ -774,23 +782,13 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
         const int* __restrict__ P = g_phases + ph * 8;
         const int b0 = P[0], b1 = P[1], g0 = P[2], g1 = P[3];
         // the hidden rows of the phase's radial MLP (P[4]; -1: none / hidden width != 64), resident for its items (item_is): requested here,
-        // first used after the staging
+        // first used -- split into halves -- after the staging, whose wait covers them, while the wave would wait for the others' staging
         const int hbr_cls = (A.hidden == 64 && A.s_split && (P[4] == 0 || (P[4] == 1 && A.h2[1]))) ? P[4] : -1;
-        IsHidden hbr;                                          // split into (hi, lo) halves once per phase, in the K-slot order of the weights' twins
+        f32x4 hv[4];                                           // (16 registers under the staging, as many as the halves they become)
         {
             const float* __restrict__ hrow = (hbr_cls == 1 ? A.h2[1] : A.h2[0]) + erow * A.hidden + 4 * g;
-            f32x4 hv[4];
 #pragma unroll
             for (int G = 0; G < 4; ++G) hv[G] = hbr_cls >= 0 ? *reinterpret_cast<const f32x4*>(hrow + 16 * G) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int s_ = 0; s_ < 8; ++s_) {
-                    const float x = hv[2 * t + (s_ >> 2)][s_ & 3] * IS_SPLIT_H_SCALE;
-                    const _Float16 h_ = (_Float16)x;
-                    hbr.hi[t][s_] = h_;
-                    hbr.lo[t][s_] = (_Float16)((x - (float)h_) * 2048.f);
-                }
         }
         __syncthreads();                                       // every wave is done with the previous blocks (and the zero fill)
         IS_T(5);                                               // waiting for the slowest wave of the previous phase
@@ -813,6 +811,43 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
 #endif
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        IsHidden hbr;                                          // split into (hi, lo) halves once per phase, in the K-slot order of the weights' twins
+        {
+            // the TILE's exponent sh (= plan.split_h_exp of the 16 edges' rows): the largest |h| of the wave's 16 x 64 values lands in [2^12, 2^13), as the
+            // weights' largest does -- whatever the rows' magnitude, nothing overflows a half and a value is flushed only below 2^-26 of the tile's largest.
+            // max |h| of a lane's 16 values in 8 instructions (v_max3_f32 with |.| on its sources: as C++ it was an AND and a MAX per value); a NaN among them is
+            // passed over (its edge's column becomes NaN whatever the exponent).  Magnitudes' bit patterns order as integers: the maximum along each DPP row
+            // by rotations, of the four rows on the scalar unit -- the same number in every wave of the workgroup, whatever the order they get here in.
+            float mf = is_absmax3(hv[0][0], hv[0][1], hv[0][2]);
+            mf = is_absmax3(mf, hv[0][3], hv[1][0]);
+            mf = is_absmax3(mf, hv[1][1], hv[1][2]);
+            mf = is_absmax3(mf, hv[1][3], hv[2][0]);
+            mf = is_absmax3(mf, hv[2][1], hv[2][2]);
+            mf = is_absmax3(mf, hv[2][3], hv[3][0]);
+            mf = is_absmax3(mf, hv[3][1], hv[3][2]);
+            mf = is_absmax3(mf, hv[3][3], hv[3][3]);
+            int mb = __builtin_bit_cast(int, mf);
+            { const int o_ = is_dpp_i<0x128>(mb); mb = o_ > mb ? o_ : mb; }       // row_ror:8, 4, 2, 1
+            { const int o_ = is_dpp_i<0x124>(mb); mb = o_ > mb ? o_ : mb; }
+            { const int o_ = is_dpp_i<0x122>(mb); mb = o_ > mb ? o_ : mb; }
+            { const int o_ = is_dpp_i<0x121>(mb); mb = o_ > mb ? o_ : mb; }
+            const int m0 = __builtin_amdgcn_readlane(mb, 0), m1 = __builtin_amdgcn_readlane(mb, 16), m2 = __builtin_amdgcn_readlane(mb, 32), m3 = __builtin_amdgcn_readlane(mb, 48);
+            const int m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3;
+            int sh = (127 + IS_SPLIT_H_TOP) - (((m01 > m23 ? m01 : m23) >> 23) & 0xff);
+            sh = sh < IS_SPLIT_H_MIN ? IS_SPLIT_H_MIN : (sh > IS_SPLIT_H_MAX ? IS_SPLIT_H_MAX : sh);
+            const float hs = __builtin_bit_cast(float, (127 + sh) << 23);
+            hbr.c0 = A.s_scale * __builtin_bit_cast(float, (127 - sh) << 23);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int s_ = 0; s_ < 8; ++s_) {
+                    const float x = hv[2 * t + (s_ >> 2)][s_ & 3] * hs;
+                    const _Float16 h_ = (_Float16)x;
+                    hbr.hi[t][s_] = h_;
+                    hbr.lo[t][s_] = (_Float16)((x - (float)h_) * 2048.f);
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);                     // (the split stays on this side of the barrier: in the wait for the other waves' staging)
         __syncthreads();
         IS_T(6);                                               // staging the phase's input blocks
         // work groups = all items of one (phase, output segment), claimed largest-first: dynamic balance, and a tile is only ever
@@ -989,7 +1024,7 @@ extern "C" int hg_tp_is(const float* const* src, const int64_t* src_stride, int 
     A.nseg = p0[1], A.nphase = p0[3], A.trash_off = p0[4], A.stage_off = p0[5], A.ctr_off = p0[6];
     A.rowtab_off = p0[8], A.rowtab_begin = p0[9], A.rowtab_len = p0[10];
     A.s_split = p0[12] == 1 && hidden == 64;
-    A.s_scale = ldexpf(1.f, -(p0[13] + IS_SPLIT_H_EXP));       // S = s_scale (S0 + 2^-11 S1): the weights' 2^sw (part record [13]) and the hidden rows' 2^sh undone
+    A.s_scale = ldexpf(1.f, -p0[13]);                          // the weights' 2^sw (part record [13]) undone; the kernel multiplies its tiles' 2^-sh in: S = 2^-(sw + sh) (S0 + 2^-11 S1)
     if (!row_table) return hg_fail(-2, "hg_tp_is: no row table");
     for (int p = 0; p < nparts; ++p) {
         const int32_t* q = part_table_host + p * IS_PART_I32;

@@ -90,14 +90,21 @@ class Program:
 # tile, fp32 accumulation in two chains, same operand bytes; the dropped lo * lo term is 2^-22 of a product.  Measured end to end on the emulator (Si2, set-A,
 # 3 layers): + 6e-7 relative on H (profiles/r06_tp_is.md).  Why the scalings: the half-precision MFMAs FLUSH SUBNORMAL INPUTS -- an unscaled lo = f16(x - hi)
 # of a weight around 0.1 is below 2^-14 and vanishes (measured: 9e-5 on H); with the remainder scaled by 2^11 the lo terms live in the range of the hi terms,
-# and 2^sw (per program: the largest |W3| lands in [2^12, 2^13)) / 2^sh (the kernel's constant for the hidden rows) keep small values normal.
+# and 2^sw (per program: the largest |W3| lands in [2^12, 2^13)) / 2^sh (per 16-edge tile and phase, chosen by the kernel from the rows it holds: split_h_exp)
+# keep small values normal.
 # The weights are split HERE (no VALU work in the kernel): every W3 fragment block [G = 4][rt][lane][q] (fp32, read by the segment-stationary kernel, the
 # emulators and the hidden != 64 path) is followed by its twin [t = 2][rt][term = hi, lo][lane][4 dwords], dword d of lane (g, i) = the K-slots (2d, 2d + 1)
 # of half t packed as two f16 (low half-word first), slot s = 4 (G - 2t) + q: the SAME (lane, slot) -> hidden unit map as the fp32 fragments, so the kernel's
 # resident hidden rows pair up with it without a shuffle.  Only for 64 (padded) hidden units.
 W3_SPLIT_MAX = 6.0e4          # a scaled weight above this is beyond the half-precision range: the launches keep the fp32 form (Program.w3_split_ok, ops.check_w3_split)
 SPLIT_LO_EXP = 11             # the remainder is scaled by 2^11 before it is rounded to half precision
-SPLIT_H_EXP = 6               # sh: the kernel scales the hidden rows by 2^6 (|h| < 1023 stays finite; hidden activations are O(1))
+# sh: the hidden rows are data -- silu MLP outputs, unbounded above, arbitrarily small near the cutoff -- so their exponent is not a constant: the kernel takes
+# it from the rows of the 16 edges it works on (split_h_exp), once per phase.  No row overflows a half, and a unit is flushed only below 2^-26 of its tile's largest.
+SPLIT_H_TOP = 12              # the largest |h| of a tile lands in [2^12, 2^13), like the weights' largest
+SPLIT_H_MIN, SPLIT_H_MAX = -100, 100     # clamp of sh: as described for 2^-88 <= max |h| < 2^113 (beyond: earlier flush below, inf / NaN above, as the fp32 form there)
+# The constant sh that the kernel used before it took the exponent from the tile (= split_h_exp of a tile whose largest |h| is in [64, 128)).  No launch uses
+# it any more; the name stays for emulators written against f16_split(h, SPLIT_H_EXP), which agree with the exact form to 2e-6 on O(1) rows only (2^-20 < |h| < 1023).
+SPLIT_H_EXP = 6
 
 
 def w3_split_index(rtm: int):
@@ -116,6 +123,15 @@ def f16_split(x: np.ndarray, exp: int = 0):
         hi = x.astype(np.float16)
         lo = ((x - hi.astype(np.float32)) * np.float32(2.0 ** SPLIT_LO_EXP)).astype(np.float16)
     return hi, lo
+
+
+def split_h_exp(rows: np.ndarray) -> int:
+    """sh of one 16-edge tile (csrc/tp_is.hip, per phase): from the exponent field of the largest |h| among the tile's hidden rows (float32; zero and fp32
+    subnormals count as exponent -127, inf as 128; a NaN is passed over unless every value is one), clamped"""
+    a = np.abs(np.ascontiguousarray(rows, dtype=np.float32)).reshape(-1)
+    a = a[~np.isnan(a)] if not np.isnan(a).all() else a
+    bits = int(a.view(np.uint32).max(initial=0))
+    return int(np.clip(127 + SPLIT_H_TOP - (bits >> 23), SPLIT_H_MIN, SPLIT_H_MAX))
 
 
 def w3_split_exp(weights: np.ndarray, regions) -> int:

@@ -52,25 +52,27 @@ S_F16 = False
 
 def _split_scale(prog, Wt32, w3, rtm, hh_cols, ne, dtype):
     """S[rt][row][edge] of one item as the kernel forms it: twin block [t][rt][hi, lo][lane][4 dwords of two halves] x the hidden rows split the same way;
-    SUBNORMAL halves count as zero (the half-precision MFMAs flush them), two accumulation chains, S = 2^-(sw + sh) (S0 + 2^-11 S1)"""
+    SUBNORMAL halves count as zero (the half-precision MFMAs flush them), two accumulation chains, S = 2^-(sw + sh) (S0 + 2^-11 S1); sh is the TILE's
+    (plan.split_h_exp of the hidden rows of its edges: slots beyond the last edge repeat it in the kernel)"""
     n = 4 * rtm * 256
     tw = Wt32[w3 + n:w3 + 2 * n].view(np.uint32).reshape(2, rtm, 2, 64, 4)
     halves = np.stack([(tw & 0xffff).astype(np.uint16), (tw >> 16).astype(np.uint16)], -1).reshape(2, rtm, 2, 64, 8).view(np.float16).astype(dtype)   # [t][rt][term][lane][slot]
     halves[np.abs(halves) < 2.0 ** -14] = 0.0
     S0, S1 = np.zeros((rtm, 16, 16), dtype=dtype), np.zeros((rtm, 16, 16), dtype=dtype)
+    sh = P.split_h_exp(hh_cols)
     for t in range(2):
         # B operand of lane (g, el), slot s: hidden unit 16 (2t + s // 4) + 4 g + s % 4 of edge el
         B = np.zeros((2, 4, 8, 16), dtype=dtype)                                          # [term][g][slot][edge]
         for g in range(4):
             for s_ in range(8):
-                hi, lo = P.f16_split(hh_cols[:, 16 * (2 * t + s_ // 4) + 4 * g + s_ % 4], P.SPLIT_H_EXP)
+                hi, lo = P.f16_split(hh_cols[:, 16 * (2 * t + s_ // 4) + 4 * g + s_ % 4], sh)
                 B[0, g, s_, :ne], B[1, g, s_, :ne] = hi.astype(dtype), lo.astype(dtype)
         B[np.abs(B) < 2.0 ** -14] = 0.0
         for rt in range(rtm):
             A = halves[t, rt].reshape(2, 4, 16, 8)                                        # [term][g][i][slot]
             S0[rt] += np.einsum("gis,gse->ie", A[0], B[0])
             S1[rt] += np.einsum("gis,gse->ie", A[0], B[1]) + np.einsum("gis,gse->ie", A[1], B[0])
-    c0 = 2.0 ** -(int(getattr(prog, "w3_exp", 0)) + P.SPLIT_H_EXP)
+    c0 = 2.0 ** -(int(getattr(prog, "w3_exp", 0)) + sh)
     return c0 * S0 + (c0 * 2.0 ** -P.SPLIT_LO_EXP) * S1
 
 

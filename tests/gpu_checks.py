@@ -133,8 +133,54 @@ def build_backbone_from_fixture(device="cuda", name="backbone"):
     return m, f
 
 
-def check_message_pack_random(device="cuda", seed=0, schedule="auto", irr=None, sh=None, radial=(16, 16), parts=None, E=83):
-    """random irreps set (odd multiplicities, missing parities) + random weights: fused MessagePackBlock on the GPU vs the fp64 oracle"""
+def scale_last_hidden_layer(module, factor, compensate=False):
+    """the last HIDDEN layer of a FullyConnectedNet weight generator (reference names: layer<i>.weight, the last one is the W3 of the edge kernels) times
+    `factor`, in place: its silu outputs -- the hidden rows -- grow with it.  compensate: the last layer divided by `factor`, so the generator's outputs keep their size"""
+    sd = module.state_dict()
+    ks = sorted((k for k in sd if k.startswith("layer") and k.endswith(".weight")), key=lambda k: int(k[5:-7]))
+    with torch.no_grad():
+        sd[ks[-2]].mul_(factor)
+        if compensate:
+            sd[ks[-1]].div_(factor)
+
+
+def _rbf_scaled(rbf, rbf_scale):
+    if rbf_scale is None:
+        return rbf
+    return rbf * (rbf_scale.to(rbf.dtype)[:, None] if torch.is_tensor(rbf_scale) else float(rbf_scale))
+
+
+def hidden_range(m, geo):
+    """the range the hidden rows of a block's two generators reach on this geometry (ops.radial_hidden on the generator weights): the largest |h|, and the
+    smallest of the rows' largest"""
+    hs = [h for h in m._hidden(geo) if h is not None]
+    return {"hidden_max_abs": max(float(h.abs().max()) for h in hs), "hidden_min_row_max_abs": min(float(h.abs().amax(1).min()) for h in hs)}
+
+
+def split_and_fp32(run):
+    """run() with the build's default radial scale (split half precision where the program has 64 hidden units), then with its fp32 form (ops.S_SPLIT_OFF)"""
+    from hamgnn_amd import ops
+    old = ops.S_SPLIT_OFF
+    try:
+        ops.S_SPLIT_OFF = False
+        a = run()
+        ops.S_SPLIT_OFF = True
+        b = run()
+    finally:
+        ops.S_SPLIT_OFF = old
+    return a, b
+
+
+def rel_or_inf(a, b):
+    """rel(a, b), inf when a holds a non-finite value"""
+    return rel(a, b) if bool(torch.isfinite(a).all()) else float("inf")
+
+
+def check_message_pack_random(device="cuda", seed=0, schedule="auto", irr=None, sh=None, radial=(16, 16), parts=None, E=83, rbf_scale=None, gen_scale=None):
+    """random irreps set (odd multiplicities, missing parities) + random weights: fused MessagePackBlock on the GPU vs the fp64 oracle.
+    rbf_scale (a float, or a tensor [E]: one factor per edge) multiplies the radial basis rows that the oracle and the kernels get: through the bias-free silu
+    generators the hidden rows scale roughly with it.  gen_scale = {"node_weight_generator" / "edge_weight_generator": factor}: the last hidden layer of that
+    generator alone.  With either, the result also holds the range the hidden rows reached, `finite`, and `rel_err_fp32` of the fp32 form of the same build."""
     from oracle import hamgnn_ref as R, e3
     from hamgnn_amd import nn as hnn, ops, plan as P
     from tests.test_plan_emu import _random_irreps
@@ -152,12 +198,14 @@ def check_message_pack_random(device="cuda", seed=0, schedule="auto", irr=None, 
     torch.set_default_dtype(torch.float64)
     try:
         ref = R.MessagePackBlock(irr, irr, sh, irr, "8x0e", radial_MLP=list(radial))
+        for name, factor in (gen_scale or {}).items():
+            scale_last_hidden_layer(getattr(ref, name), factor)
         g = torch.Generator().manual_seed(seed)
         src, dst, ef = (torch.randn(E, ref.irreps_node_feats.dim, generator=g) for _ in range(3))
         vec = torch.randn(E, 3, generator=g) * 3.0
         n = torch.nn.functional.normalize(vec, dim=-1)
         shv = e3.spherical_harmonics(list(range(lsh + 1)), n, True, "component")
-        rbf = torch.randn(E, 8, generator=g)
+        rbf = _rbf_scaled(torch.randn(E, 8, generator=g), rbf_scale)
         out = ref(src, dst, ef, shv, rbf).detach()
     finally:
         torch.set_default_dtype(prev)
@@ -166,13 +214,13 @@ def check_message_pack_random(device="cuda", seed=0, schedule="auto", irr=None, 
     if parts is not None:                                      # workgroups per 16-edge tile (1: the large-graph path)
         os.environ["HG_IS_PARTS"] = str(parts)
     try:
-        return _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef, out, E)
+        return _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef, out, E, ranged=rbf_scale is not None or gen_scale is not None)
     finally:
         os.environ.pop("HG_MP_KERNEL", None)
         os.environ.pop("HG_IS_PARTS", None)
 
 
-def _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef, out, E):
+def _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef, out, E, ranged=False):
     from hamgnn_amd import ops, plan as P
     m.compile(device, unrotate=True)
     lay = P.PlanarLayout(irr)
@@ -191,15 +239,23 @@ def _message_pack_random_run(m, device, irr, sh, lmax, lsh, n, rbf, src, dst, ef
     scale = out.abs().max().item()
     dp = m._dp_for(E)
     kern = "seg" if dp.sched is None else "is"
+    if ranged:                                                 # (no floor on the output's scale here: small rows are what these cases are about)
+        y, y32 = split_and_fp32(lambda: ops.from_planar(m.run(xs, xd, fe, geo), imap))
+        torch.cuda.synchronize()
+        rows = (y.double().cpu() - out).abs().amax(1) / out.abs().amax(1)
+        return {"irreps": irr, "sh": sh, "kernel": kern, "parts_used": dp.is_parts_for(E) if dp.sched is not None else 0, **hidden_range(m, geo), "out_max_abs": scale,
+                "finite": bool(torch.isfinite(y).all()), "rel_err": rel_or_inf(y, out), "rel_err_fp32": rel_or_inf(y32, out), "worst_row_rel_err": float(rows.max())}
     return {"irreps": irr, "sh": sh, "kernel": kern, "rel_err": 0.0 if scale < 1e-12 else rel(y, out)}
 
 
-def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedule="auto", E=83, radial=(16, 16), parts=None, gather=False):
+def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedule="auto", E=83, radial=(16, 16), parts=None, gather=False, rbf_scale=None):
     """SURVEY 8f-3 (first step): data gradient of one MessagePackBlock forward on the GPU (adjoint program on the same HIP kernels) vs
     torch.autograd through the fp64 oracle.  Random irreps set unless given.
     parts: workgroups per 16-edge tile forced for the adjoint launch (HG_IS_PARTS; 1 = the large-graph launch `tp_is_kernel<false, false>`).
     gather: the output gradient is drawn as NODE rows [7, D] and handed over with `gather=receivers`, as the backbone hands the gradient of
-    a ConvBlock's aggregate (gathered and rotated inside the kernel's staging); the oracle's loss reads the gathered rows."""
+    a ConvBlock's aggregate (gathered and rotated inside the kernel's staging); the oracle's loss reads the gathered rows.
+    rbf_scale: as in check_message_pack_random (the adjoint programs' radial scales are formed by the same kernel code from the same hidden rows); the result then
+    also holds the hidden rows' range, `finite`, and the three errors of the fp32 form of the same build (`*_fp32`)."""
     from oracle import hamgnn_ref as R, e3
     from hamgnn_amd import nn as hnn, ops, plan as P
     from tests.test_plan_emu import _random_irreps
@@ -222,7 +278,7 @@ def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedu
         vec = torch.randn(E, 3, generator=g) * 3.0
         n = torch.nn.functional.normalize(vec, dim=-1)
         shv = e3.spherical_harmonics(list(range(lsh + 1)), n, True, "component")
-        rbf = torch.randn(E, 8, generator=g)
+        rbf = _rbf_scaled(torch.randn(E, 8, generator=g), rbf_scale)
         N_ = 7
         G = torch.randn(N_ if gather else E, ref.irreps_node_feats.dim, generator=g)
         recv = torch.randint(0, N_, (E,), generator=g) if gather else None
@@ -252,7 +308,8 @@ def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedu
         os.environ["HG_IS_PARTS"] = str(parts)
     try:
         m.compile_adjoint(device)
-        gs, gd, gf = m.backward_data(ops.to_planar(G.float().to(device), imap, lay.dim), geo, out_is_global=True, gather=geo.dst if gather else None)
+        run = lambda: m.backward_data(ops.to_planar(G.float().to(device), imap, lay.dim), geo, out_is_global=True, gather=geo.dst if gather else None)
+        (gs, gd, gf), g32 = split_and_fp32(run) if rbf_scale is not None else (run(), None)
         dpa = m.programs()[("adjoint", False)]
         parts_used = dpa.is_parts_for(E) if dpa.sched is not None else 0       # what the launch above asked the schedule for (an int, or "lds")
     finally:
@@ -262,10 +319,18 @@ def check_message_pack_backward(device="cuda", seed=0, irr=None, sh=None, schedu
     torch.cuda.synchronize()
     scale = max(float(t.grad.abs().max()) for t in (src, dst, ef))
     err = lambda a, t: 0.0 if scale < 1e-12 else float((ops.from_planar(a, imap).double().cpu() - t.grad).abs().max()) / scale
-    return {"irreps": irr, "sh": sh, "kernel": "is" if dpa.sched is not None else "seg",
-            "parts": int(dpa.sched.part_table.shape[0]) if dpa.sched is not None else 0,
-            "parts_used": parts_used, "fixed_parts": dpa.fixed_parts, "E": E, "gather": bool(gather),
-            "g_src_rel_err": err(gs, src), "g_dst_rel_err": err(gd, dst), "g_edge_rel_err": err(gf, ef)}
+    out = {"irreps": irr, "sh": sh, "kernel": "is" if dpa.sched is not None else "seg",
+           "parts": int(dpa.sched.part_table.shape[0]) if dpa.sched is not None else 0,
+           "parts_used": parts_used, "fixed_parts": dpa.fixed_parts, "E": E, "gather": bool(gather),
+           "g_src_rel_err": err(gs, src), "g_dst_rel_err": err(gd, dst), "g_edge_rel_err": err(gf, ef)}
+    if rbf_scale is not None:                                  # (no floor on the gradients' scale here: small rows are what these cases are about)
+        errf = lambda a, t: float((ops.from_planar(a, imap).double().cpu() - t.grad).abs().max()) / scale if bool(torch.isfinite(a).all()) else float("inf")
+        g32 = (g32[0], g32[1], ops.rotate_gather(g32[2], None, geo, rot, transpose=True))
+        torch.cuda.synchronize()
+        out.update(hidden_range(m, geo), grad_max_abs=scale, finite=all(bool(torch.isfinite(a).all()) for a in (gs, gd, gf)))
+        for name, a, a32, t in (("g_src", gs, g32[0], src), ("g_dst", gd, g32[1], dst), ("g_edge", gf, g32[2], ef)):
+            out[name + "_rel_err"], out[name + "_rel_err_fp32"] = errf(a, t), errf(a32, t)
+    return out
 
 
 def check_message_pack_weight_grads(device="cuda", seed=0, irr=None, sh=None, E=53, radial=(16, 16), num_radial=8, fp32_ref=False):
@@ -1736,11 +1801,13 @@ def check_head_su2(device="cuda"):
 
 
 def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, nao=19, num_layers=2, radial=(16, 16), num_radial=8,
-                         n_graphs=1, legacy_edge_update=False, zs=(14, 8, 6, 1), soc=False, isolated=False, graph=None, parts=None):
+                         n_graphs=1, legacy_edge_update=False, zs=(14, 8, 6, 1), soc=False, isolated=False, graph=None, parts=None, gen_scale=None):
     """Seeded random weights on a synthetic periodic cell: full backbone + head, HIP (fp32) vs oracle (fp64, CPU).
     graph="hub": hub_graph() instead of a random cell (one receiver over three tiles, single-edge receivers, atoms without edges, a ragged tail).
     parts: workgroups per 16-edge tile forced for every input-stationary launch (HG_IS_PARTS; 1 = the large-graph launches with the node scatter fused into the
-    ConvBlocks' edge kernel); the message-block launches the forward issued are then in the result (`launches`)."""
+    ConvBlocks' edge kernel); the message-block launches the forward issued are then in the result (`launches`).
+    gen_scale = (conv block, generator name, factor): that generator's last hidden layer times `factor` and its last layer divided by it -- the block's hidden rows
+    grow, its weights' magnitude stays; the result then holds the range those rows reached on the HIP side and `finite`."""
     from oracle import hamgnn_ref as R
     from hamgnn_amd.data import synthetic as S
     from hamgnn_amd.models.hamgnn_conv import HamGNNConvE3
@@ -1755,6 +1822,8 @@ def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, n
     try:
         ref = R.HamGNNConvE3(cfg)
         ref_head = R.HamGNNPlusPlusOut(irreps, irreps, nao_max=nao, ham_type="openmx", symmetrize=True, add_H0=True, soc_switch=soc)
+        if gen_scale is not None:
+            scale_last_hidden_layer(getattr(ref.convolutions[gen_scale[0]].conv_tp, gen_scale[1]), gen_scale[2], compensate=True)
     finally:
         torch.set_default_dtype(prev)
     if graph == "hub":
@@ -1793,6 +1862,10 @@ def oracle_vs_hip_random(device="cuda", irreps=MINI, sh=SH, n_atoms=6, seed=0, n
            "H_rel_err": rel(H, H_ref), "H_mae": (H.double().cpu() - H_ref).abs().mean().item()}
     if parts is not None:
         out["launches"] = [l for l in launches if l["tag"] == "message_pack"]
+    if gen_scale is not None:
+        out.update(hidden_range(hip.convolutions[gen_scale[0]].conv_tp, rep["_geometry"]), finite=bool(torch.isfinite(H).all() and torch.isfinite(rep["node_attr"]).all()))
+        for k in ("node_rel_err", "edge_rel_err", "H_rel_err"):
+            out[k] = out[k] if out["finite"] else float("inf")
     return out
 
 

@@ -111,7 +111,8 @@ def test_radial_scale_split_half_precision_twins_vs_oracle(monkeypatch):
     the kernel's resident hidden rows are).  (1) hi + lo reproduces the fp32 weight to 2^-21; (2) the device-side refresh (ops.DeviceProgram.refresh_w3_split
     with the torch twin of hg_w3_split_refill) writes the same bytes as the host packer; (3) the emulator fed from the TWINS (the kernel's arithmetic: W_lo h_hi + W_hi h_lo + W_hi h_hi) agrees
     with the fp64 oracle to 3e-6 and with the exact-table form to 2e-6 -- but not to 1e-9: the path is exercised; (4) a weight beyond the half-precision
-    range clears the part record's flag."""
+    range clears the part record's flag; (5) the HIDDEN ROWS' twins: the exponent is the tile's own (plan.split_h_exp, as the kernel picks it from the 16 edges'
+    rows), so on both sides of the old fixed exponent's edges (|h| = 1023 above, 2^-20 below) hi + 2^-11 lo reproduces h 2^sh to 22 bits with finite halves."""
     import torch
     from oracle import hamgnn_ref as R, e3
     from hamgnn_amd import ops
@@ -157,6 +158,26 @@ def test_radial_scale_split_half_precision_twins_vs_oracle(monkeypatch):
             hi[np.abs(hi) < 2.0 ** -14], lo[np.abs(lo) < 2.0 ** -14] = 0.0, 0.0          # what the matrix pipe sees
             # 22 bits relative; below the halves' normal range an absolute floor of 2^-24 in scaled units = 2^-36 of the largest weight
             assert (np.abs(hi + lo * 2.0 ** -11 - w) <= 2.0 ** -21 * np.abs(w) + 2.0 ** -24).all()
+    # (5) the hidden rows' split rule.  A tile's rows: `top` is its largest |h|, next to it values on each side of the edges of the fixed 2^6 that this
+    # replaced (1023 / 1024: overflow; 2^-20: hi a subnormal half), signs mixed, and units down to 2^-30 of the largest
+    for top in (2.0 ** -40, 2.0 ** -30, 0.9 * 2.0 ** -20, 2.0 ** -20, 1.1 * 2.0 ** -20, 1e-3, 1.0, 1022.0, 1023.0, 1023.9, 1024.0, 1025.0, 2047.0, 16384.0, 65504.0, 65520.0, 1e6, 1e30):
+        row = np.float32(top) * np.array([1.0, -0.999, 0.75, -1.0 / 3.0, 0.1, 2.0 ** -9, -2.0 ** -12 * 1.3, 2.0 ** -20 / 3, -2.0 ** -25 * 1.7, 2.0 ** -26 * 1.01, 2.0 ** -26 * 0.99, 2.0 ** -30, 0.0], dtype=np.float32)
+        sh_t = P.split_h_exp(row.reshape(1, -1))
+        y = row.astype(np.float64) * 2.0 ** sh_t
+        assert 2.0 ** P.SPLIT_H_TOP <= np.abs(y).max() < 2.0 ** (P.SPLIT_H_TOP + 1), (top, sh_t)
+        hi, lo = (v.astype(np.float64) for v in P.f16_split(row, sh_t))
+        assert np.isfinite(hi).all() and np.isfinite(lo).all(), top
+        hi[np.abs(hi) < 2.0 ** -14], lo[np.abs(lo) < 2.0 ** -14] = 0.0, 0.0              # what the matrix pipe sees
+        err = np.abs(hi + lo * 2.0 ** -11 - y)
+        kept = np.abs(y) >= 2.0 ** -14
+        # kept units: 22 bits relative + the flushed remainder's floor (2^-25 in scaled units); a unit is dropped whole only below 2^-26 of the tile's largest
+        assert (err[kept] <= 2.0 ** -21 * np.abs(y[kept]) + 2.0 ** -25).all(), (top, err)
+        assert (err[~kept] <= np.abs(y[~kept]) + 2.0 ** -25).all() and (np.abs(row[~kept]) < 2.0 ** -26 * np.abs(row).max()).all(), top
+        assert kept[:10].all()
+    assert P.split_h_exp(np.zeros((16, 64), np.float32)) == P.SPLIT_H_MAX and P.split_h_exp(np.full((1, 4), np.inf, np.float32)) == P.SPLIT_H_MIN
+    assert P.split_h_exp(np.array([[1.0, np.nan]], np.float32)) == P.SPLIT_H_TOP          # a NaN is passed over: its edge's scale is a NaN whatever the exponent
+    # the constant that the tile's exponent replaced is the tile rule's value for 64 <= max |h| < 128, and is what overflows from 1024 on
+    assert P.split_h_exp(np.array([[64.0, -127.9]], np.float32)) == P.SPLIT_H_EXP and not np.isfinite(P.f16_split(np.array([1024.0], np.float32), P.SPLIT_H_EXP)[0]).all()
     # (2) device-side refresh == host packer, byte for byte
     dp = ops.DeviceProgram(prog, torch.device("cpu"), schedule="is")
     want = prog.weights.copy()
