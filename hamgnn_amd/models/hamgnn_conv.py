@@ -65,9 +65,10 @@ def _cfg_get(c, k, default=None):
     return getattr(c, k, default)
 
 
-class _BackboneBase(nn.Module):
+class _BackboneBase(hnn.CompiledModule, nn.Module):
     """What HamGNNConvE3 and HamGNNTransformer share (hamgnn_conv.py:89-190 == hamgnn_transformer.py:37-112): config keys, atomic /
-    pair / chemical embedding, per-edge geometry, and the lazily converted result dict."""
+    pair / chemical embedding, per-edge geometry, the lazily converted result dict, and the life cycle of what is packed from the weights
+    (compile / refresh_weights over the blocks that a backbone lists in _blocks())."""
 
     _kan_built = False                                         # which backbones run HamGNN_pre.use_kan (the others refuse it in _init_common)
 
@@ -125,13 +126,48 @@ class _BackboneBase(nn.Module):
         self.chemical_embedding = nn.Module()
         self.chemical_embedding.linear = hnn.E3Linear(Irreps([(self.num_types, 0, 1)]), D)
         self.layout = P.PlanarLayout(D)
-        self._compiled_for = None
+        self._compiled_for = None                              # the device everything below was packed for (None: pack at the next forward)
+        self._pending_refresh = False                          # an optimiser stepped since the last forward: refresh_weights() at the next one
+        self._struct_for = None                                # the device of the structural tables: index map, rotate table, Wigner J table
+        self._imap = self._rot_tab = self._jtab = None
+        self._chem = None                                      # the chemical embedding as a planar row table
+        self._last_delta = None                                # the charge-doping correction of the forward under way
+        self._edge_alive = None                                # declare_consumer: the (l, p) classes of the edge rows that the last pair block still computes
         return g
+
+    def _blocks(self):
+        """the blocks of the layers, each with compile(device) and refresh(device)"""
+        raise NotImplementedError
+
+    def compile(self, device):
+        """(Re)pack all weights into MFMA fragment order and upload.  Call again after changing parameters."""
+        dev = torch.device(device)
+        for b in self._blocks():
+            b.compile(dev)
+        self._compile_common(dev)
+        return self
+
+    def refresh_at_next_forward(self):
+        """the optimiser steps AFTER training_step returns: the refresh waits for the forward that follows (training.weights_changed)"""
+        self._pending_refresh = True
+
+    def refresh_weights(self):
+        """after an optimiser step (hamgnn_amd.training): bring the uploaded programs up to date WITHOUT the host planner -- the message blocks by a
+        device-side repack (hamgnn_amd/repack.py), the Linear tables in place, the small embedding tables rebuilt on the host (< 1 ms each)"""
+        dev = self._compiled_for
+        if dev is None:
+            return
+        if self.lite_mode or self.use_kan:
+            self._compiled_for = None                          # full recompile on the next forward
+            return
+        for b in self._blocks():
+            b.refresh(dev)
+        self._compile_common(dev)
 
     def _compile_common(self, dev):
         self.pair_embedding.compile(dev)
         lay = self.layout
-        if getattr(self, "_struct_for", None) != dev:          # structural tables: once per device (not per repack)
+        if self._struct_for != dev:                            # structural tables: once per device (not per repack)
             self._imap = torch.from_numpy(lay.index_map().astype(np.int32)).to(dev)
             self._rot_tab = torch.from_numpy(P.rotate_table(lay)).to(dev)
             self._jtab = torch.from_numpy(P.wigner_jtab(self.lmax)).to(dev)
@@ -153,7 +189,7 @@ class _BackboneBase(nn.Module):
         """-> (z, topology, geometry, node [N, Dp] planar, f [E, Dp] planar in the edge frame)"""
         ops.require_fp32(self, data)                           # `precision: 64` raises instead of returning fp32-accurate rows
         dev = data.pos.device
-        if getattr(self, "_pending_refresh", False):           # an optimiser stepped since the last forward (training.weights_changed)
+        if self._pending_refresh:                              # an optimiser stepped since the last forward (training.weights_changed)
             self._pending_refresh = False
             self.refresh_weights()
         if self._compiled_for != dev:
@@ -215,8 +251,6 @@ class _BackboneBase(nn.Module):
         return rep
 
     # ---- unread irreps of the last PairInteractionBlock (r5)
-    _edge_alive = None
-
     def declare_consumer(self, head):
         """Tell the backbone that `head` is the ONLY reader of the representation it returns (what `Model(representation, output)` wires: Model.py:459-465 of
         the reference passes the representation to the output module and nowhere else).  If the head can say which (l, p) classes of the edge rows it reads
@@ -357,39 +391,10 @@ class HamGNNConvE3(_BackboneBase):
                 pair.conv_tp.set_structural_zeros(node=(), edge=zero_edge)
                 zero_edge = ()
 
+    def _blocks(self):
+        return [*self.convolutions, *(self.corr_products if self.use_corr_prod else ()), *self.pair_interactions]
+
     # ------------------------------------------------------------------------------------------------------------
-    def compile(self, device):
-        """(Re)pack all weights into MFMA fragment order and upload.  Call again after changing parameters."""
-        dev = torch.device(device)
-        for c, p in zip(self.convolutions, self.pair_interactions):
-            c.compile(dev)
-            p.compile(dev)
-        if self.use_corr_prod:
-            for c in self.corr_products:
-                c.compile(dev)
-        self._compile_common(dev)
-        return self
-
-    def refresh_weights(self):
-        """after an optimiser step (hamgnn_amd.training): bring the uploaded programs up to date WITHOUT the host planner for the
-        message blocks (device-side repack, hamgnn_amd/repack.py); the small Linear / embedding tables are rebuilt on the host (< 1 ms each)"""
-        dev = self._compiled_for
-        if dev is None:
-            return
-        if self.lite_mode or self.use_kan:
-            self._compiled_for = None                          # full recompile on the next forward
-            return
-        if self.use_corr_prod:
-            for c in self.corr_products:
-                c.compile(dev)                                 # four Linear tables + the concatenated element weights (host, ~ms)
-        for conv, pair in zip(self.convolutions, self.pair_interactions):
-            conv.residual.refresh(dev)                         # (its two Linears + the cached fused chain; the gate tables are structural)
-            conv.skip_linear.compile(dev)
-            if not conv.conv_tp.refresh():
-                conv.conv_tp.compile(dev, unrotate=True)
-            pair.refresh(dev)
-        self._compile_common(dev)
-
     def forward(self, data, save_for_backward: bool = False):
         """save_for_backward: keep the layer inputs (node rows, edge rows, aggregated messages) on the result (`_tape`) for `backward`"""
         if save_for_backward and self.use_kan:

@@ -19,7 +19,7 @@ from ..so3 import Irreps
 from ..topo import get_topology, gget, ghas, gset
 
 
-class HamGNNPlusPlusOut(nn.Module):
+class HamGNNPlusPlusOut(hnn.CompiledModule, nn.Module):
     def __init__(self, irreps_in_node=None, irreps_in_edge=None, nao_max=14, return_forces=False, create_graph=False,
                  ham_type="openmx", ham_only=False, symmetrize=True, include_triplet=False, calculate_band_energy=False,
                  num_k=8, k_path=None, band_num_control=None, soc_switch=True, nonlinearity_type="gate",
@@ -56,7 +56,14 @@ class HamGNNPlusPlusOut(nn.Module):
         self.hamiltonian_irreps = P.ham_irreps(self.row)
         self.node_layout = P.PlanarLayout(irreps_in_node)
         self.edge_layout = P.PlanarLayout(irreps_in_edge)
-        self._compiled_for = None
+        self._compiled_for = None                              # the device the HamLayers were packed for (None: pack at the next forward)
+        # STRUCTURAL tables on the device (functions of the basis and the layouts, not of the weights): built by compile(), once per device
+        self._struct_for = None
+        self._slot = self._cg = self._slot_su2 = self._cg_su2 = None           # CG merge maps (so3 / su2)
+        self._mask = self._orank = self._num_valence = self._norb = self._defined = self._basis_sig = None      # basis tables by atomic number
+        self._n_imap = self._e_imap = self._rot_tab = self._lmax = self._jtab = self._blk = None                # layouts, frames, shell blocks
+        self._adj_tabs_by = {}                                 # (so3 | su2, device) -> the merge maps transposed, for backward()
+        self._unshifted = None                                 # zero_point_shift with a band loss: the rows of the forward before the shift
         if soc_switch and self.soc_basis == "su2":
             # hamgnn_output.py:281-293 + :189-198: irreps_out = 2 * (required + required); get_H reads copies 0 (re) and 2 (im)
             half = P.su2_irreps(self.row)
@@ -83,12 +90,11 @@ class HamGNNPlusPlusOut(nn.Module):
     # ------------------------------------------------------------------------------------------------------------
     def compile(self, device):
         dev = torch.device(device)
-        self._adj_tabs = None
         for m in self.children():
             if isinstance(m, hnn.HamLayer):
                 m.compile(dev)
         su2 = self.soc_switch and self.soc_basis == "su2"
-        if getattr(self, "_struct_for", None) == dev:          # everything below is STRUCTURAL (basis tables, CG maps, layouts): built once per device;
+        if self._struct_for == dev:                            # everything below is STRUCTURAL (basis tables, CG maps, layouts): built once per device;
             self._compiled_for = dev                           # a recompile after an optimiser step only repacks the HamLayers' weights above
             return self
         net = self.onsite_overlap_network if (su2 and not self.ham_only) else self.onsite_hamiltonian_network
@@ -409,7 +415,7 @@ class HamGNNPlusPlusOut(nn.Module):
         dev = g_on.device
         # structural tables (CG merge maps: functions of the basis, not of the weights): built once per (key, table object) -- rebuilding them
         # after every optimiser step put a device -> host copy in the middle of the step
-        cache = self.__dict__.setdefault("_adj_tabs_by", {})
+        cache = self._adj_tabs_by
         key = (key, str(tables[0].device))                     # (per device: an id()-keyed entry outlives its tables and could be recycled)
         if key not in cache:
             glay = P.PlanarLayout(net_on.girr)

@@ -9,7 +9,6 @@ input-stationary MFMA kernel (the same K2 launch as a ConvBlockE3's, un-rotated 
 csrc/attention.hip) and the Gate ResidualBlock with the skip row added in its last Linear's epilogue."""
 from __future__ import annotations
 
-import torch
 from torch import nn
 
 from .. import nn as hnn
@@ -36,26 +35,8 @@ class HamGNNTransformer(_BackboneBase):
         self.orb_transformers[0].conv_tp_value.set_structural_zeros(node=zero_node, edge=zero_edge)
         self.pair_interactions[0].conv_tp.set_structural_zeros(node=(), edge=zero_edge)
 
-    def compile(self, device):
-        dev = torch.device(device)
-        for a, c, p in zip(self.orb_transformers, self.corr_products, self.pair_interactions):
-            a.compile(dev)
-            c.compile(dev)
-            p.compile(dev)
-        self._compile_common(dev)
-        return self
-
-    def refresh_weights(self):
-        """after an optimiser step (hamgnn_amd.training): as HamGNNConvE3.refresh_weights -- message blocks repacked on the device, the
-        small tables on the host"""
-        dev = self._compiled_for
-        if dev is None:
-            return
-        for att, corr, pair in zip(self.orb_transformers, self.corr_products, self.pair_interactions):
-            att.refresh(dev)
-            corr.compile(dev)
-            pair.refresh(dev)
-        self._compile_common(dev)
+    def _blocks(self):
+        return [*self.orb_transformers, *self.corr_products, *self.pair_interactions]
 
     def forward(self, data, save_for_backward: bool = False):
         """save_for_backward: keep the layer inputs on the result (`_tape`) for `backward`"""

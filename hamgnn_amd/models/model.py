@@ -53,9 +53,10 @@ def load_reference_state_dict(module: nn.Module, state_dict: Dict[str, torch.Ten
     with torch.no_grad():
         for k, p in params.items():
             p.copy_(sd[k].to(p.dtype).reshape(p.shape))
+    from ..nn import CompiledModule
     for m in module.modules():                                 # weights changed: packed MFMA fragments are stale
-        if hasattr(m, "_compiled_for"):
-            m._compiled_for = None
+        if isinstance(m, CompiledModule):
+            m.drop_compiled()
     return unexpected
 
 

@@ -55,10 +55,48 @@ def o3_linear_weight_grad(irreps_in, irreps_out, x_planar: torch.Tensor, gy_plan
     return torch.cat(out) if out else x_planar.new_zeros(0)
 
 
+class DeviceState:
+    """mixin of every module that keeps weight-derived state on the device.  hamgnn_amd.training reaches that state through these methods and
+    nothing else: a module that grows a cache answers for it here, in its own weights_changed()"""
+
+    def weights_changed(self):
+        """the optimiser stepped: mark or drop what was packed from the weights (rebuilt at the next use)"""
+        raise NotImplementedError
+
+    def enable_row_program(self):
+        """(only the holders of a fused inference chain have something to switch back on: _RowProgramHolder)"""
+
+
+class _RowProgramHolder(DeviceState):
+    """a module that caches a fused inference chain (csrc/rowprog.hip): `_rowprog` = None (not built yet) | False (no kernel form / switched off) | an
+    ops.DeviceRowProgram built from the weights of its moment; `_rowprog_off` is sticky across recompiles -- the 0.1 s host build per step is not worth it
+    while the weights move (the backward re-evaluates the stages one by one anyway), validation inside a training run stays on the separate kernels"""
+
+    def weights_changed(self):
+        self._rowprog, self._rowprog_off = None, True
+
+    def enable_row_program(self):
+        self._rowprog, self._rowprog_off = None, False
+
+
+class CompiledModule(DeviceState):
+    """a module whose forward packs its whole subtree when `_compiled_for` is not the device of the batch (the two backbones, the read-out head)"""
+
+    def drop_compiled(self):
+        self._compiled_for = None
+
+    weights_changed = drop_compiled
+
+
 _LINEAR_PACKERS: Dict[tuple, object] = {}
 
 
-class E3Linear(nn.Module):
+def _linear_stream() -> bool:
+    """HG_LINEAR_KERNEL = stream (default: csrc/linear.hip) | seg (the Linear as a program of the segment-stationary kernel)"""
+    return os.environ.get("HG_LINEAR_KERNEL", "stream") != "seg"
+
+
+class E3Linear(DeviceState, nn.Module):
     """o3.Linear parameter holder: flat weight, paths ordered (i_in, i_out), each (mul_in, mul_out) row-major."""
 
     def __init__(self, irreps_in, irreps_out):
@@ -66,9 +104,19 @@ class E3Linear(nn.Module):
         self.irreps_in, self.irreps_out = Irreps(irreps_in), Irreps(irreps_out)
         n = sum(mi * mo for (mi, li, pi) in self.irreps_in for (mo, lo, po) in self.irreps_out if (li, pi) == (lo, po))
         self.weight = nn.Parameter(torch.randn(n))
-        self._dp = None
+        self._dp = self._dp_adj = None                         # forward / adjoint tables, each built on first use
+        self._stale = False                                    # the weights moved since the tables were packed: brought up to date at the next use
 
-    _stale = False                                             # the weights moved since the tables were packed (training._invalidate): refresh on next use
+    def weights_changed(self):
+        if isinstance(self._dp, ops.DeviceLinear) and self._dp.refreshable:
+            self._stale = True                                 # refreshed on the device at the next use (compile)
+        else:
+            self._dp = self._dp_adj = None
+
+    def forward_fused_elsewhere(self):
+        """this Linear's forward runs inside its owner's program (the skip o3.Linear of a PairInteractionBlock: extra items of the message block): only
+        backward_data uses the module's own (adjoint) tables, and brings them up to date when it next runs"""
+        self._stale = True
 
     def _packer(self, adjoint: bool):
         """blob = const + coef * weight[idx] of the (adjoint) streaming-Linear tables, discovered once per (irreps pair, direction) by probing the
@@ -83,15 +131,19 @@ class E3Linear(nn.Module):
                                                  OrderedDict(w=int(self.weight.numel())))
         return _LINEAR_PACKERS[key]
 
+    def _refresh(self, dl, adjoint: bool) -> bool:
+        """refresh in place on the device, else rebuild on the host -- decided here and nowhere else: the weight blob of the uploaded tables `dl` rewritten
+        from the weights of the moment; False: `dl` is absent or not refreshable, the caller rebuilds (or drops) it"""
+        if not (isinstance(dl, ops.DeviceLinear) and dl.refreshable):
+            return False
+        dl.weights.copy_(self._packer(adjoint).apply({"w": self.weight.detach()}))
+        return True
+
     def compile(self, device):
         self._stale = False
-        stream = os.environ.get("HG_LINEAR_KERNEL", "stream") != "seg"
-        if stream and isinstance(self._dp, ops.DeviceLinear) and self._dp.weights.device == torch.device(device) and getattr(self._dp, "refreshable", False):
-            w = {"w": self.weight.detach()}                    # already uploaded: refresh the weight blobs in place, on the device
-            self._dp.weights.copy_(self._packer(False).apply(w))
-            if getattr(self, "_dp_adj", None) is not None and getattr(self._dp_adj, "refreshable", False):
-                self._dp_adj.weights.copy_(self._packer(True).apply(w))
-            else:
+        stream = _linear_stream()
+        if stream and self._dp is not None and self._dp.weights.device == torch.device(device) and self._refresh(self._dp, False):
+            if not self._refresh(self._dp_adj, True):
                 self._dp_adj = None
             return self
         W = self.weight.detach().cpu().double().numpy()
@@ -99,8 +151,7 @@ class E3Linear(nn.Module):
         if not stream:                                         # HG_LINEAR_KERNEL=seg: the Linear as a program of the segment-stationary kernel
             self._dp = ops.DeviceProgram(P.build_linear_program(W, self.irreps_in, self.irreps_out), device)
         else:                                                  # default: the streaming block-Linear kernel (csrc/linear.hip)
-            self._dp = ops.DeviceLinear(P.build_linear_tables(W, self.irreps_in, self.irreps_out, keep_zero_blocks=True), device)
-            self._dp.refreshable = True
+            self._dp = ops.DeviceLinear(P.build_linear_tables(W, self.irreps_in, self.irreps_out, keep_zero_blocks=True), device, refreshable=True)
         return self
 
     def forward(self, x_planar: torch.Tensor, res=()) -> torch.Tensor:
@@ -116,18 +167,15 @@ class E3Linear(nn.Module):
     #      a plain reduction over the rows (one library GEMM per path)
     def backward_data(self, gy_planar: torch.Tensor) -> torch.Tensor:
         dev = gy_planar.device
-        adj = getattr(self, "_dp_adj", None)
-        if adj is not None and self._stale and getattr(adj, "refreshable", False) and self._dp is None:
-            adj.weights.copy_(self._packer(True).apply({"w": self.weight.detach()}))    # (a Linear whose forward is fused elsewhere: only these tables exist)
-            self._stale = False
-        elif self._stale:
-            self.compile(dev)
-            adj = getattr(self, "_dp_adj", None)
-        if adj is None:
+        if self._stale:
+            if self._dp is None and self._refresh(self._dp_adj, True):      # (a Linear whose forward is fused elsewhere: only these tables exist)
+                self._stale = False
+            else:
+                self.compile(dev)
+        if self._dp_adj is None:
             W = self.weight.detach().cpu().double().numpy()
-            adj = self._dp_adj = ops.DeviceLinear(P.build_linear_adjoint_tables(W, self.irreps_in, self.irreps_out, keep_zero_blocks=True), dev)
-            adj.refreshable = True
-        return ops.linear_planar(adj, gy_planar, tag="linear_adjoint")
+            self._dp_adj = ops.DeviceLinear(P.build_linear_adjoint_tables(W, self.irreps_in, self.irreps_out, keep_zero_blocks=True), dev, refreshable=True)
+        return ops.linear_planar(self._dp_adj, gy_planar, tag="linear_adjoint")
 
     def weight_grad(self, x_planar: torch.Tensor, gy_planar: torch.Tensor) -> torch.Tensor:
         return o3_linear_weight_grad(self.irreps_in, self.irreps_out, x_planar, gy_planar)
@@ -292,7 +340,7 @@ class _Uploaded(NamedTuple):
     uses_skip: bool        # the blob holds the fused skip o3.Linear
 
 
-class MessagePackBlock(nn.Module):
+class MessagePackBlock(DeviceState, nn.Module):
     def __init__(self, irreps_node_feats, irreps_edge_feats, irreps_local_env_edge, irreps_out, num_radial, radial_MLP=(64, 64),
                  lite_mode=False, use_kan=False):
         super().__init__()
@@ -335,6 +383,10 @@ class MessagePackBlock(nn.Module):
         self._adj_maps = None
         self._lite_bw = None
         self._wg_prev, self._wg = (self._wg or self._wg_prev), None     # the device constants of the weight gradients are handed over (adopt_constants)
+
+    def weights_changed(self):
+        """(a block whose owner has no refresh path: nothing is refreshed in place while `_dp` is None, the owner's next compile() packs anew)"""
+        self._dp = None
 
     def programs(self) -> Dict[tuple, object]:
         """read-only: {key: device object} of what this block holds on the device now (keys as in _reset)"""
@@ -665,7 +717,7 @@ class MessagePackBlock(nn.Module):
                             rot_mask=0b011, reduce=reduce)
 
 
-class ResidualBlock(nn.Module):
+class ResidualBlock(_RowProgramHolder, nn.Module):
     def __init__(self, irreps_in, feature_irreps_hidden, resnet=True, nonlinearity_type="gate"):
         """interaction_blocks.py:262-358.  nonlinearity_type "gate" (e3nn Gate; every block of the backbone, the head's default) or "norm" (e3nn
         NormActivation with ShiftedSoftPlus as given, normalize, epsilon 1e-8: the head's HamLayers under `nonlinearity_type: norm`, :311-330)"""
@@ -682,41 +734,43 @@ class ResidualBlock(nn.Module):
         self.linear1 = E3Linear(self.irreps_in, self.gate_in)
         self.linear2 = E3Linear(self.gate_out, self.irreps_in)
         self.resnet = resnet
-        self._tab = None
+        self._tab = self._cst = None                           # activation tables / constants on the device (structural): compile()
+        self._rowprog, self._rowprog_off = None, False         # the fused inference chain: _RowProgramHolder
 
     def compile(self, device):
-        self.linear1.compile(device)
-        self.linear2.compile(device)
         if self.nonlinearity_type == "norm":
             self._tab = torch.from_numpy(self._tab_np).contiguous().to(device)
         else:
             self._tab = tuple(torch.from_numpy(t).contiguous().to(device) for t in P.gate_tables_compact(self._tab_np))
         self._cst = torch.from_numpy(P.ACT_CONSTS).to(device)
-        self._rowprog = None                                   # the fused inference chain is built on first use, from the weights of that moment
-        self._rowprog_off = getattr(self, "_rowprog_off", False)   # set by training._invalidate: separate kernels while the weights move
-        return self
+        return self.refresh(device)
 
     def refresh(self, device):
-        """after an optimiser step: the two Linears' tables rebuilt on the host (the gate tables are structural) and the cached fused chain DROPPED -- it was
-        built from the weights of its moment, so validate -> step -> validate ran the pre-step weights through it"""
+        """everything that depends on the weights (compile() adds the structural gate tables): the two Linears' tables, and the cached fused chain DROPPED -- it
+        was built from the weights of its moment, so validate -> step -> validate ran the pre-step weights through it; rebuilt on first use"""
         self.linear1.compile(device)
         self.linear2.compile(device)
         self._rowprog = None
+        return self
+
+    def _row_stages(self):
+        """(the stages Linear1 -> Gate -> Linear2 (+ x) of plan.build_row_program from the weights of the moment, the layout of the rows they map onto themselves)"""
+        w = lambda m: m.weight.detach().cpu().double().numpy()
+        li, lgi, lgo = P.PlanarLayout(self.irreps_in), P.PlanarLayout(self.gate_in), P.PlanarLayout(self.gate_out)
+        return [("linear", P.o3_linear_mats(w(self.linear1), self.irreps_in, self.gate_in), li, lgi, False),
+                ("gate", self._tab_np, lgi.dim, lgo.dim),
+                ("linear", P.o3_linear_mats(w(self.linear2), self.gate_out, self.irreps_in), lgo, li, bool(self.resnet))], li
 
     def _row_program(self, device):
         """Linear1 -> Gate -> Linear2 (+ x) as ONE row program (csrc/rowprog.hip; late r5: the node-level chain of a ConvBlock is launch-bound on small
         crystals -- three launches become one), or False (HG_ROWPROG=0 / HG_NODE_ROWPROG=0, "norm" activation, no kernel form, weights moving)"""
-        if getattr(self, "_rowprog", None) is None:
+        if self._rowprog is None:
             self._rowprog = False
-            if (os.environ.get("HG_ROWPROG", "1") != "0" and os.environ.get("HG_NODE_ROWPROG", "1") != "0" and not getattr(self, "_rowprog_off", False)
+            if (os.environ.get("HG_ROWPROG", "1") != "0" and os.environ.get("HG_NODE_ROWPROG", "1") != "0" and not self._rowprog_off
                     and self.nonlinearity_type == "gate" and isinstance(self.linear1._dp, ops.DeviceLinear)):
-                w = lambda m: m.weight.detach().cpu().double().numpy()
-                li, lgi, lgo = P.PlanarLayout(self.irreps_in), P.PlanarLayout(self.gate_in), P.PlanarLayout(self.gate_out)
                 try:
-                    rp = P.build_row_program([("linear", P.o3_linear_mats(w(self.linear1), self.irreps_in, self.gate_in), li, lgi, False),
-                                              ("gate", self._tab_np, lgi.dim, lgo.dim),
-                                              ("linear", P.o3_linear_mats(w(self.linear2), self.gate_out, self.irreps_in), lgo, li, bool(self.resnet))], li.dim)
-                    self._rowprog = ops.DeviceRowProgram(rp, device)
+                    stages, li = self._row_stages()
+                    self._rowprog = ops.DeviceRowProgram(P.build_row_program(stages, li.dim), device)
                 except NotImplementedError:
                     pass
         return self._rowprog
@@ -770,6 +824,13 @@ class ConvBlockE3(nn.Module):
         self.conv_tp.compile(device, unrotate=True)
         self.skip_linear.compile(device)
 
+    def refresh(self, device):
+        """after an optimiser step: the Linear tables refreshed in place, the message block's programs repacked on the device (hamgnn_amd/repack.py)"""
+        self.residual.refresh(device)
+        self.skip_linear.compile(device)
+        if not self.conv_tp.refresh():
+            self.conv_tp.compile(device, unrotate=True)
+
 
 class AttentionBlockE3(nn.Module):
     """AttentionBlockE3 of the reference (hamgnn/nn/attention.py:167-360), parameter names included.  `linear_query` and `max_radius`
@@ -788,6 +849,7 @@ class AttentionBlockE3(nn.Module):
         self.conv_tp_value = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP)
         self.linear_key, self.linear_query = E3Linear(irreps, irreps), E3Linear(irreps, irreps)
         self.skip_linear = E3Linear(irreps, irreps)
+        self._head_tab = self._cut = None                      # channel -> head table (structural) and the cutoff parameter on the device: compile()
 
     def compile(self, device):
         for m in (self.linear_up_src, self.linear_up_tar, self.linear_up_edge, self.residual, self.linear_key, self.skip_linear):
@@ -895,6 +957,7 @@ class PairInteractionBlock(nn.Module):
         self.conv_tp = MessagePackBlock(irreps, irreps, irreps_sh, irreps, num_radial, radial_MLP, lite_mode, use_kan)
         if use_skip_connections:
             self.skip_linear = E3Linear(irreps, irreps)
+        self._up_both = None                                   # linear_up_both's merged tables: None (not built) | False (no such form) | ops.DeviceLinear
 
     def compile(self, device):
         self._up_both = None
@@ -909,14 +972,14 @@ class PairInteractionBlock(nn.Module):
             self.conv_tp.compile(device, unrotate=False, skip_weight=skip,   # skip o3.Linear fused as extra items
                                  skip_source=(self.skip_linear,) if self.use_skip_connections else None)
             if self.use_skip_connections:
-                self.skip_linear._stale = True                 # its forward is fused above; only the backward uses the module's own (adjoint) tables
+                self.skip_linear.forward_fused_elsewhere()
 
 
     def linear_up_both(self, node):
         """(linear_up_src(node), linear_up_tar(node)) as ONE launch: an o3.Linear into the doubled irreps, the two results are the halves of its rows
         (views with the doubled row stride -- the edge kernel gathers node rows by pointer + stride).  Inference only: built from the weights of the moment,
         dropped by compile() / refresh() (late r5: small crystals are launch-bound)."""
-        if getattr(self, "_up_both", None) is None:
+        if self._up_both is None:
             self._up_both = False
             if os.environ.get("HG_NODE_ROWPROG", "1") != "0" and isinstance(self.linear_up_src._dp, ops.DeviceLinear):
                 irr = self.linear_up_src.irreps_in
@@ -942,7 +1005,7 @@ class PairInteractionBlock(nn.Module):
         if not self.conv_tp.refresh(skip=skip):
             self.compile(device)
         elif self.use_skip_connections:
-            self.skip_linear._stale = True
+            self.skip_linear.forward_fused_elsewhere()
 
 
 class _EmbTP(nn.Module):
@@ -961,7 +1024,7 @@ class _EmbTP(nn.Module):
         self.weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.linear_scaler.weight_numel], use_kan)
 
 
-class PairInteractionEmbeddingBlock(nn.Module):
+class PairInteractionEmbeddingBlock(DeviceState, nn.Module):
     def __init__(self, num_types, irreps_sh, irreps_out, num_radial, radial_MLP, lite_mode=False, use_kan=False):
         super().__init__()
         self.num_types, self.lite_mode, self.use_kan = num_types, lite_mode, bool(use_kan)
@@ -970,9 +1033,13 @@ class PairInteractionEmbeddingBlock(nn.Module):
         self.linear_up_src = E3Linear(attrs, attrs)
         self.linear_up_dst = E3Linear(attrs, attrs)
         self.conv_tp = _EmbTP(attrs, self.irreps_sh, self.irreps_out, num_radial, radial_MLP, lite_mode, use_kan)
-        self._dp = self._h = self._sd_np = None                # set by compile()
+        self._dp = self._h = self._sd_np = self._Ts = self._Td = None      # set by compile()
+        self._Tp = P.PlanarLayout([(num_types, 0, 1)]).dim
         self._wgrad = self._wgrad_prev = None                  # [backward_mp.TPWeightGrad, its two materialisation programs] of the compiled weights, and the one before
         self._fused_bw = None                                  # (the TPWeightGrad they belong to, fused weight-gradient tables, adjoint program)
+
+    def weights_changed(self):
+        self._dp = None                                        # (`_wgrad` is handed over by compile(): its device constants are reused)
 
     def compile(self, device):
         T = self.num_types
@@ -984,7 +1051,6 @@ class PairInteractionEmbeddingBlock(nn.Module):
         self._sd_np = _np_sd(self.conv_tp)
         self._dp = ops.DeviceProgram(P.build_embedding_program(self._sd_np, T, self.irreps_sh, self.irreps_out, self.lite_mode), device)
         self._h = self.conv_tp.weight_generator.hidden_layers(device)
-        self._Tp = P.PlanarLayout([(T, 0, 1)]).dim
         self._wgrad_prev, self._wgrad = (self._wgrad or self._wgrad_prev), None     # (device constants handed over: adopt_constants)
 
     def backward(self, z, geo: ops.Geometry, g_f, chunk: int = 65536, delta=None):
@@ -1107,7 +1173,7 @@ class ChargeEmbedding(nn.Module):
         return self._mlp(attrs) - self._mlp(self.neutral_charge_attrs.expand(attrs.size(0), -1))
 
 
-class HamLayer(nn.Module):
+class HamLayer(_RowProgramHolder, nn.Module):
     def __init__(self, irreps_in, ham_irreps: Irreps, keep=None, nonlinearity_type="gate"):
         """keep: optional bool per output irrep -- outputs the caller never reads (they keep their weights, for checkpoint
         compatibility, but no GEMM rows are spent on them; SOC/su2 head).  nonlinearity_type: of the ResidualBlock (hamgnn_output.py:38-58)."""
@@ -1115,6 +1181,16 @@ class HamLayer(nn.Module):
         self.irreps_in, self.ham_irreps, self.keep = Irreps(irreps_in), ham_irreps, keep
         self.residual_block = ResidualBlock(irreps_in, irreps_in, nonlinearity_type=nonlinearity_type)
         self.linear_transform = E3Linear(irreps_in, ham_irreps)
+        # linear_transform runs on the block's OWN tables (outputs regrouped by (L, p): not E3Linear's), packed on the host and not refreshable
+        self._dp = self._dp_adj = None                         # forward tables (compile()) / adjoint tables (first backward())
+        self._W_np = None                                      # the weight they were packed from, on the host
+        self.girr = self.slot_pos = None                       # the regrouped output irreps and the slots' places in them, as compile() found them
+        self._slot_gather_tab = None                           # _slot_gather: structural, once per device
+        self._rowprog, self._rowprog_off = None, False         # the fused inference chain: _RowProgramHolder
+
+    def weights_changed(self):
+        self._dp = self._dp_adj = None
+        super().weights_changed()
 
     def input_irreps_read(self):
         """the (l, parity) classes of the INPUT rows this network's result depends on.  Every map of the chain connects equal (l, p) only -- o3.Linear by
@@ -1128,10 +1204,9 @@ class HamLayer(nn.Module):
         self.residual_block.compile(device)
         self._dp_adj = None
         self._rowprog = None                                   # the fused chain (csrc/rowprog.hip) is built on first use, from the weights of that moment
-        self._rowprog_off = getattr(self, "_rowprog_off", False)    # set by training._invalidate: separate kernels while the weights move
         W = self.linear_transform.weight.detach().cpu().double().numpy()
         self._W_np = W                                         # kept for backward(): a device -> host copy there would drain the queue mid-step
-        stream = os.environ.get("HG_LINEAR_KERNEL", "stream") != "seg"
+        stream = _linear_stream()
         if all(m == 1 for m, _, _ in self.ham_irreps):         # hamiltonian irreps: regroup the multiplicity-1 outputs by (L,p)
             if stream:
                 mats, self.girr, self.slot_pos = P.ham_linear_mats(W, self.irreps_in, self.ham_irreps, self.keep)
@@ -1149,7 +1224,7 @@ class HamLayer(nn.Module):
     def _slot_gather(self, girr, slot_pos, dev):
         """(index into [flat weight gradient of o3.Linear(irreps_in -> girr) | 0], scale) that give linear_transform.weight's gradient: the reference's
         paths (i_in, slot) are columns of the (i_in, group) blocks, normalised by the slot's fan-in instead of the group's.  Structure only: cached."""
-        cur = getattr(self, "_slot_gather_tab", None)
+        cur = self._slot_gather_tab
         if cur is None or cur[0] != str(dev):
             girr = Irreps(girr)
             paths = [(i, g) for i, (_, l1, p1) in enumerate(self.irreps_in) for g, (_, l2, p2) in enumerate(girr) if (l1, p1) == (l2, p2)]
@@ -1186,11 +1261,9 @@ class HamLayer(nn.Module):
         (g_x, {parameter name: gradient in the reference's flat layout})"""
         if not isinstance(self._dp, ops.DeviceLinear):
             raise NotImplementedError("HamLayer.backward: streaming Linear path only (HG_LINEAR_KERNEL=seg has no adjoint tables)")
-        W_host = lambda: self._W_np if getattr(self, "_W_np", None) is not None else self.linear_transform.weight.detach().cpu().double().numpy()
         if self.slot_pos is None:                               # xi networks: a plain o3.Linear (e.g. irreps_in -> nao^2 x 0e)
-            W = W_host()
-            if getattr(self, "_dp_adj", None) is None:
-                self._dp_adj = ops.DeviceLinear(P.build_linear_adjoint_tables(W, self.irreps_in, self.ham_irreps), x_planar.device)
+            if self._dp_adj is None:
+                self._dp_adj = ops.DeviceLinear(P.build_linear_adjoint_tables(self._W_np, self.irreps_in, self.ham_irreps), x_planar.device)
             y = self.residual_block(x_planar)
             g_y = ops.linear_planar(self._dp_adj, g_out_planar, tag="linear_adjoint")
             g_x, g_res = self.residual_block.backward(x_planar, g_y)
@@ -1199,8 +1272,8 @@ class HamLayer(nn.Module):
             return g_x, grads
         girr, slot_pos = self.girr, self.slot_pos              # (structure: as compile() found it)
         dev = x_planar.device
-        if getattr(self, "_dp_adj", None) is None:
-            mats = P.ham_linear_mats(W_host(), self.irreps_in, self.ham_irreps, self.keep)[0]
+        if self._dp_adj is None:
+            mats = P.ham_linear_mats(self._W_np, self.irreps_in, self.ham_irreps, self.keep)[0]
             self._dp_adj = ops.DeviceLinear(P.linear_tables({(g, i): M.T for (i, g), M in mats.items()}, P.PlanarLayout(girr),
                                                             P.PlanarLayout(self.irreps_in)), dev)
         y = self.residual_block(x_planar)
@@ -1219,23 +1292,18 @@ class HamLayer(nn.Module):
     def _row_program(self, device):
         """Linear1 -> Gate -> Linear2 (+ x) -> linear_transform as ONE row program (plan.build_row_program), or False when the chain has no
         kernel form (HG_ROWPROG=0, channel counts beyond the kernel's unit shape, LDS)"""
-        if getattr(self, "_rowprog", None) is None:
+        if self._rowprog is None:
             self._rowprog = False
-            if (os.environ.get("HG_ROWPROG", "1") != "0" and not getattr(self, "_rowprog_off", False) and isinstance(self._dp, ops.DeviceLinear)
+            if (os.environ.get("HG_ROWPROG", "1") != "0" and not self._rowprog_off and isinstance(self._dp, ops.DeviceLinear)
                     and self.residual_block.nonlinearity_type == "gate"):      # (the row program has a gate stage only: "norm" runs Linear / hg_norm_act / Linear)
-                rb = self.residual_block
-                w = lambda m: m.weight.detach().cpu().double().numpy()
-                li, lgi, lgo = P.PlanarLayout(self.irreps_in), P.PlanarLayout(rb.gate_in), P.PlanarLayout(rb.gate_out)
+                W = self.linear_transform.weight.detach().cpu().double().numpy()
                 if self.slot_pos is not None:
-                    m3 = P.ham_linear_mats(w(self.linear_transform), self.irreps_in, self.ham_irreps, self.keep)[0]
+                    m3 = P.ham_linear_mats(W, self.irreps_in, self.ham_irreps, self.keep)[0]
                 else:
-                    m3 = P.o3_linear_mats(w(self.linear_transform), self.irreps_in, self.ham_irreps)
+                    m3 = P.o3_linear_mats(W, self.irreps_in, self.ham_irreps)
                 try:
-                    rp = P.build_row_program([("linear", P.o3_linear_mats(w(rb.linear1), self.irreps_in, rb.gate_in), li, lgi, False),
-                                              ("gate", rb._tab_np, lgi.dim, lgo.dim),
-                                              ("linear", P.o3_linear_mats(w(rb.linear2), rb.gate_out, self.irreps_in), lgo, li, bool(rb.resnet)),
-                                              ("linear", m3, li, P.PlanarLayout(self.girr), False)], li.dim)
-                    self._rowprog = ops.DeviceRowProgram(rp, device)
+                    stages, li = self.residual_block._row_stages()
+                    self._rowprog = ops.DeviceRowProgram(P.build_row_program(stages + [("linear", m3, li, P.PlanarLayout(self.girr), False)], li.dim), device)
                 except NotImplementedError:
                     pass
         return self._rowprog
@@ -1306,9 +1374,13 @@ class CorrProductBlock(nn.Module):
         Ks = [self._tab_np[f"K{nu}"] for nu in range(1, correlation + 1)]
         self.prod = _ProductBasis(self.irreps_hidden, num_elements, Ks, num_hidden_features)
         self.linear_out = E3Linear(self.irreps_hidden, self.irreps)
-        self._tab = None
+        self._tab = None                                       # the contraction tables on the device (structural: once per device)
+        self._W1 = self._W2 = self._W3 = self._W4 = None       # the element weights of nu = 1 ... 4, the target irreps' blocks concatenated: compile()
+        self._hdim = P.PlanarLayout(self.irreps_hidden).dim
 
     def compile(self, device):
+        """everything of the block that depends on the weights, and on first use the structural tables; cheap enough (four Linear tables refreshed in place +
+        the concatenated element weights) to serve as refresh() after every optimiser step"""
         for m in (self.linear_pre, self.linear_sc, self.prod.linear, self.linear_out):
             m.compile(device)
         d, cur = torch.device(device), (self._tab["ell_off"].device if self._tab is not None else None)
@@ -1321,8 +1393,9 @@ class CorrProductBlock(nn.Module):
         self._W2 = cat(2) if self.correlation >= 2 else torch.zeros(self._W1.shape[0], 1, self._W1.shape[2], device=device)
         self._W3 = cat(3) if self.correlation >= 3 else None
         self._W4 = cat(4) if self.correlation >= 4 else None
-        self._hdim = P.PlanarLayout(self.irreps_hidden).dim
         return self
+
+    refresh = compile
 
     @staticmethod
     def _generic_kernels():

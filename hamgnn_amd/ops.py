@@ -132,6 +132,8 @@ class DeviceProgram:
         self._device = device
         self._is_tables = {}                                   # parts -> (IsSchedule, device tables)
         self._is_weights = {}                                  # parts -> weight blob with the schedule's own streams appended (lite_mode runs)
+        self._w3_idx = None                                    # refresh_w3_split's index tensors (structural: built on first use)
+        self._w3_split_off = False                             # check_w3_split: a refreshed W3 weight left the half-precision range
         if prog.vsegs and schedule not in ("is", "is_parts"):
             raise ValueError("a program with merged items runs on the input-stationary kernel only")
         self.fixed_parts = None                                # "lds": the tiles of all output segments need several workgroups per 16 edges
@@ -155,10 +157,10 @@ class DeviceProgram:
         """the split-half-precision twins of the W3 fragment blocks (plan/program.py:w3_split_fill) recomputed ON THE DEVICE from the fp32 blocks of the blob --
         the device-side repack (hamgnn_amd/repack.py) is affine in the parameters, hi = f16(x) / lo = f16(x - hi) is not.  Whether every weight is inside the
         half-precision range is checked lazily, by ONE host read before the next launch (check_w3_split): outside it the launches keep the fp32 form."""
-        regs = getattr(self.prog, "w3_regions", None)
+        regs = self.prog.w3_regions
         if not regs:
             return
-        if getattr(self, "_w3_idx", None) is None:
+        if self._w3_idx is None:
             se, so, dh, dl = [], [], [], []
             for off, rtm in regs:
                 n = 4 * rtm * 256
@@ -166,12 +168,12 @@ class DeviceProgram:
                 se.append(off + src[:, 0]); so.append(off + src[:, 1]); dh.append(off + n + dst[0]); dl.append(off + n + dst[1])
             self._w3_idx = tuple(_dev(np.concatenate(a).astype(np.int64), self._device) for a in (se, so, dh, dl))
         se, so, dh, dl = self._w3_idx
-        sc_, lo_ = float(2.0 ** int(getattr(self.prog, "w3_exp", 0))), float(2.0 ** P.SPLIT_LO_EXP)
+        sc_, lo_ = float(2.0 ** int(self.prog.w3_exp)), float(2.0 ** P.SPLIT_LO_EXP)
         W3_SPLIT_PENDING.append((self, w3_split_refill(self.weights, se, so, dh, dl, sc_, lo_)))
 
     def part_table_host(self, sc) -> np.ndarray:
         """the schedule's part table as the launch passes it in host memory: [12] (W3 split twins present) cleared when a refreshed weight left the half-precision range"""
-        if (getattr(self, "_w3_split_off", False) or S_SPLIT_OFF) and int(sc.part_table[0][12]):
+        if (self._w3_split_off or S_SPLIT_OFF) and int(sc.part_table[0][12]):
             pt = sc.part_table.copy()
             pt[:, 12] = 0
             return pt
@@ -217,8 +219,11 @@ class DeviceProgram:
 class DeviceLinear:
     """plan.LinearTables uploaded to the GPU (hg_linear_planar)"""
 
-    def __init__(self, tabs: P.LinearTables, device):
+    def __init__(self, tabs: P.LinearTables, device, refreshable: bool = False):
+        """refreshable: the tables keep their zero blocks, so that the weight blob is an affine map of the flat weight with a fixed structure and can be
+        rewritten in place after an optimiser step (nn.E3Linear._refresh)"""
         self.tabs = tabs
+        self.refreshable = bool(refreshable)
         self.nitems = int(tabs.items.shape[0])
         self.items, self.units, self.paths = _dev(tabs.items, device), _dev(tabs.units, device), _dev(tabs.paths, device)
         self.weights = _dev(tabs.weights, device)

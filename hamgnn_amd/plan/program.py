@@ -54,6 +54,8 @@ class Program:
     seg_key: Dict[int, int] = field(default_factory=dict)
     # r6: radial-scale operands in SPLIT HALF PRECISION (see w3_split_fill): (float offset of a W3 fragment block, row tiles); its split twin follows it directly
     w3_regions: List[Tuple[int, int]] = field(default_factory=list)
+    w3_exp: int = 0                                   # the twins hold W3 2^w3_exp; set by finalize() (the default: a program without W3 blocks, or a probe_dtype run)
+    w3_split_ok: bool = True                          # every scaled weight is inside the half-precision range (W3_SPLIT_MAX)
 
     def add_weights(self, arr: np.ndarray) -> int:
         arr = np.ascontiguousarray(arr, dtype=_WEIGHT_DTYPE[0]).reshape(-1)

@@ -150,8 +150,8 @@ def is_schedule(prog: "Program", parts=1, separate_mlp: Optional[bool] = None) -
     hp4 = prog.hidden_pad // 4
     nseg = prog.seg_table.shape[0]
     lite_flag = int(np.isin(prog.item_table[:, 0], (IT_LINC, IT_LINM, IT_POST)).any())      # lite_mode items run in their own kernel instantiation
-    s_split = int(bool(getattr(prog, "w3_regions", None)) and getattr(prog, "w3_split_ok", True))      # part record [12]: W3 blocks carry their split-half-precision twins,
-    s_exp = int(getattr(prog, "w3_exp", 0))                                                              # [13]: scaled by 2^[13] (plan/program.py:w3_split_fill)
+    s_split = int(bool(prog.w3_regions) and prog.w3_split_ok)      # part record [12]: W3 blocks carry their split-half-precision twins,
+    s_exp = int(prog.w3_exp)                                       # [13]: scaled by 2^[13] (plan/program.py:w3_split_fill)
     if lite_flag and np.isin(prog.item_table[:, 0], (IT_TP, IT_LIN)).any():
         raise NotImplementedError("input-stationary schedule: a program mixes lite_mode items with tensor-product / Linear items")
     key_of = [prog.seg_key.get(sg, sg) for sg in range(nseg)]   # segments written by merged items share one work-group key

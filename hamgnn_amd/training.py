@@ -181,7 +181,7 @@ def weights_changed(model):
     rep = getattr(model, "representation", None)
     if rep is not None and hasattr(rep, "refresh_weights"):
         _invalidate(model.output_module)
-        rep._pending_refresh = True                            # the optimiser steps AFTER training_step returns: refresh at the next forward
+        rep.refresh_at_next_forward()                          # the optimiser steps AFTER training_step returns
     else:
         _invalidate(model)
 
@@ -207,29 +207,21 @@ def allreduce_gradients(model, average: bool = True):
 
 
 def _invalidate(module):
-    """the packed weight fragments / adjoint tables are stale once the optimiser has stepped: repacked on the next forward"""
-    from .nn import E3Linear
+    """the packed weight fragments / adjoint tables are stale once the optimiser has stepped: every module that holds some marks or drops its own
+    (nn.DeviceState.weights_changed), repacked on the next forward"""
+    from .nn import DeviceState
     for m in module.modules():
-        if isinstance(m, E3Linear) and m._dp is not None and getattr(m._dp, "refreshable", False):
-            m._stale = True                                    # its tables are refreshed on the device at the next use (nn.E3Linear.compile)
-            continue
-        for attr in ("_dp", "_dp_adj", "_adj_tabs"):             # (`_wgrad` is handed over by the blocks' compile(): its device constants are reused)
-            if attr in vars(m):                                # (an attribute the instance holds, not a read-only view of its class)
-                setattr(m, attr, None)
-        if hasattr(m, "_rowprog"):                             # HamLayer's fused inference chain: its 0.1 s host build per step is not worth it while
-            m._rowprog = None                                  # the weights move (the backward re-evaluates the stages one by one anyway)
-            m._rowprog_off = True
-        if hasattr(m, "_compiled_for"):
-            m._compiled_for = None
+        if isinstance(m, DeviceState):
+            m.weights_changed()
 
 
 def enable_row_programs(module):
     """after training: let the HamLayers build their fused inference chains (csrc/rowprog.hip) again -- _invalidate switches them off while the
     weights move, and the flag is sticky (validation / inference inside a training run stay on the separate kernels)"""
+    from .nn import DeviceState
     for m in module.modules():
-        if hasattr(m, "_rowprog_off"):
-            m._rowprog_off = False
-            m._rowprog = None
+        if isinstance(m, DeviceState):
+            m.enable_row_program()
 
 
 @torch.no_grad()

@@ -616,11 +616,46 @@ MESSAGE_PACK_PROGRAM_KINDS = [("forward", False, False), ("forward", False, True
                               ("adjoint", False), ("adjoint", True), ("wgrad fused", False), ("wgrad fused", True)]
 
 
-def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=False, radial=(16, 16), num_types=20):
+def _attribute_census(seen, changed, *models):
+    """the attribute names of every module of `models`, and of every ops.DeviceLinear / DeviceProgram / DeviceRowProgram that a module holds as an attribute
+    (directly, or inside a tuple / list / dict it holds), against what the same object held when it was first seen (`seen`: id -> (object, names); the object
+    is kept, so that an id is not reused).  Names that came or went are added to `changed`: {class name: set of names}.  No class is excluded."""
+    from hamgnn_amd import ops
+    holders = (ops.DeviceLinear, ops.DeviceProgram, ops.DeviceRowProgram)
+
+    def held(v, depth=0):
+        if isinstance(v, holders):
+            yield v
+        elif depth < 3 and isinstance(v, (tuple, list, dict)):
+            for x in (v.values() if isinstance(v, dict) else v):
+                yield from held(x, depth + 1)
+
+    for model in models:
+        for m in model.modules():
+            for o in [m] + [h for v in list(vars(m).values()) for h in held(v)]:
+                now = set(vars(o))
+                first = seen.setdefault(id(o), (o, now))[1]
+                if now != first:
+                    changed.setdefault(type(o).__name__, set()).update(now ^ first)
+
+
+def _row_programs_held(module, cls):
+    """how many modules of exactly the class `cls` under `module` hold a fused inference chain now"""
+    from hamgnn_amd import ops
+    return sum(isinstance(m._rowprog, ops.DeviceRowProgram) for m in module.modules() if type(m) is cls)
+
+
+def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=False, radial=(16, 16), num_types=20, use_corr_prod=False, lifecycle=False):
     """training: after an optimiser step the message blocks repack their weights on the device (hamgnn_amd/repack.py).  A model that
     took a step, had ALL parameters perturbed and was refreshed must give the loss and every gradient of a freshly compiled model with
     the same parameters.  radial=(16, 64), num_types=24: the fused weight-gradient route, with which a first-layer block holds every kind of
-    program -- "kinds" counts the backbone's message blocks that hold each at the moment the weights move, "embedding_fused_route" says that the pair embedding took it too."""
+    program -- "kinds" counts the backbone's message blocks that hold each at the moment the weights move, "embedding_fused_route" says that the pair embedding took it too.
+    use_corr_prod: a CorrProductBlock after every ConvBlock of the ConvE3 backbone (the transformer always has them): its concatenated element weights are
+    weight-derived state too.
+    lifecycle: the run goes on after the inference that follows the step -- "rowprogs_while_training" counts the HamLayers that hold a fused chain there
+    (the flag that training sets is sticky: none); then training.enable_row_programs on both models and a third inference: "enabled_rel_diff", and the
+    HamLayers / the backbone's ResidualBlocks that hold a chain now ("enabled_ham_rowprogs", "enabled_residual_rowprogs").  "attributes_changed":
+    {class: names} of every attribute that came or went after construction, on any module or uploaded table of either model, over the whole run."""
     import copy
     from hamgnn_amd.data import synthetic as S
     from hamgnn_amd.models.hamgnn_conv import HamGNNConvE3
@@ -629,7 +664,7 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
     from hamgnn_amd.training import training_step
     cfg = dict(num_types=num_types, irreps_edge_sh=SH, edge_sh_normalization="component", edge_sh_normalize=True, build_internal_graph=False,
                cutoff=26.0, rbf_func="bessel", num_radial=8, num_layers=2, irreps_node_features=MINI, use_kan=False, radial_MLP=list(radial),
-               correlation=2, num_hidden_features=4, use_corr_prod=False, legacy_edge_update=legacy)
+               correlation=2, num_hidden_features=4, use_corr_prod=use_corr_prod, legacy_edge_update=legacy)
     irr = "8x0e+4x0o+4x1o+2x1e+2x2o+4x2e+2x3o" if transformer else MINI
     if transformer:
         from hamgnn_amd.models.hamgnn_transformer import HamGNNTransformer
@@ -640,11 +675,16 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
                                                  soc_switch=False, calculate_sparsity=False, zero_point_shift=False))
     torch.manual_seed(21)
     a = mk().to(device)
+    seen, changed = {}, {}
+    census = (lambda *models: _attribute_census(seen, changed, *models)) if lifecycle else (lambda *models: None)
+    census(a)                                                   # right after construction
     g = S.add_random_targets(S.random_cell(6, [14, 8, 6, 1], seed=2, density=0.004), 19, seed=2).to(device)
     target = 0.1 * torch.randn(g.num_nodes + g.num_edges, 19 * 19, generator=torch.Generator().manual_seed(3)).to(device)
     with torch.no_grad():
         H_pre = a(g)["hamiltonian"].clone()                     # an INFERENCE forward first: builds the cached fused chains (ResidualBlock / HamLayer row programs)
+    census(a)
     training_step(a, g, metric="mse", target=target)            # builds every program (forward, adjoint, weight-gradient), marks them stale
+    census(a)
     from hamgnn_amd.nn import MessagePackBlock
     kinds = {}                                                  # what the BACKBONE's message blocks hold now, when the weights move: what refresh() has to repack
     for m in a.representation.modules():
@@ -657,10 +697,12 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
             p.add_(0.05 * torch.randn(p.shape, generator=gen).to(device))
             p.grad = None
     b = mk().to(device)
+    census(b)                                                   # right after construction
     b.load_state_dict(copy.deepcopy(a.state_dict()))
     ra = training_step(a, g, metric="mse", target=target)
     refreshed = sum(len(m._packers) for m in a.modules() if isinstance(m, MessagePackBlock))
     rb = training_step(b, g, metric="mse", target=target)
+    census(a, b)
     # validate -> step -> validate: an inference forward of the stepped model must use the NEW weights everywhere, also in the chains that
     # were cached by the inference forward before the step
     with torch.no_grad():
@@ -668,8 +710,23 @@ def check_refresh_equals_recompile(device="cuda", legacy=False, transformer=Fals
     torch.cuda.synchronize()
     pa, pb = dict(a.named_parameters()), dict(b.named_parameters())
     worst = max(float((pa[k].grad - pb[k].grad).abs().max()) / max(float(pb[k].grad.abs().max()), 1e-6) for k in pb)
-    return {"packers": refreshed, "loss_rel_diff": abs(float(ra["loss"]) - float(rb["loss"])) / abs(float(rb["loss"])), "grad_max_rel_diff": worst,
-            "inference_rel_diff": rel(Ha, Hb), "step_moved_H": rel(H_pre, Hb), "kinds": kinds, "embedding_fused_route": fb is not None and fb[1] is not None}
+    out = {"packers": refreshed, "loss_rel_diff": abs(float(ra["loss"]) - float(rb["loss"])) / abs(float(rb["loss"])), "grad_max_rel_diff": worst,
+           "inference_rel_diff": rel(Ha, Hb), "step_moved_H": rel(H_pre, Hb), "kinds": kinds, "embedding_fused_route": fb is not None and fb[1] is not None}
+    if lifecycle:
+        from hamgnn_amd.nn import HamLayer, ResidualBlock
+        from hamgnn_amd.training import enable_row_programs
+        census(a, b)
+        out["rowprogs_while_training"] = _row_programs_held(a, HamLayer) + _row_programs_held(b, HamLayer)
+        enable_row_programs(a)
+        enable_row_programs(b)
+        with torch.no_grad():
+            Ha, Hb = a(g)["hamiltonian"].clone(), b(g)["hamiltonian"].clone()
+        torch.cuda.synchronize()
+        census(a, b)
+        out.update(enabled_rel_diff=rel(Ha, Hb), enabled_ham_rowprogs=_row_programs_held(a, HamLayer),
+                   enabled_residual_rowprogs=_row_programs_held(a.representation, ResidualBlock),
+                   attributes_changed={k: sorted(v) for k, v in changed.items()}, objects_watched=len(seen))
+    return out
 
 
 def check_conv_message_backward(device="cuda", n_atoms=10, seed=2):

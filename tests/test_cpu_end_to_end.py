@@ -108,6 +108,31 @@ def test_device_repack_equals_recompile_every_program_kind(cpu_backend, transfor
     assert r["inference_rel_diff"] < 1e-6 and r["step_moved_H"] > 1e-3, r
 
 
+@pytest.mark.parametrize("kw", [dict(use_corr_prod=True), dict(transformer=True)], ids=["conv_corr_prod", "transformer"])
+def test_weight_lifecycle_of_the_node_level_modules(cpu_backend, kw):
+    """inference, step, perturb, step, inference, enable_row_programs, inference on a backbone with CorrProductBlocks (their concatenated element weights are
+    weight-derived state, like every Linear table and fused chain): the refreshed model equals a freshly compiled one at the bars of the cases above; the flag
+    that switches the fused inference chains off while the weights move is sticky until training.enable_row_programs, after which they are built again -- from
+    the new weights; and no module or uploaded table gains or loses an attribute after its construction (nn.Module adds none of its own: no exception)."""
+    r = G.check_refresh_equals_recompile(device="cpu", lifecycle=True, **kw)
+    print(r)
+    assert r["packers"] >= 8 and r["loss_rel_diff"] < 1e-6 and r["grad_max_rel_diff"] < 1e-5, r
+    assert r["inference_rel_diff"] < 1e-6 and r["step_moved_H"] > 1e-3, r
+    assert r["rowprogs_while_training"] == 0, r
+    assert r["enabled_rel_diff"] < 1e-6 and r["enabled_ham_rowprogs"] >= 1, r
+    if "transformer" not in kw:                                # (an AttentionBlockE3 runs its ResidualBlock stage by stage: only ConvBlockE3's holds a fused chain)
+        assert r["enabled_residual_rowprogs"] >= 1, r
+    assert r["attributes_changed"] == {} and r["objects_watched"] > 100, r
+
+
+def test_training_reaches_module_state_through_the_protocol_only():
+    """hamgnn_amd.training pokes no module by attribute name: invalidation goes through nn.DeviceState"""
+    import inspect
+    import hamgnn_amd.training as T
+    src = inspect.getsource(T)
+    assert not any(s in src for s in ("vars(", "setattr(", "hasattr(m")), [s for s in ("vars(", "setattr(", "hasattr(m") if s in src]
+
+
 def test_merged_compile_falls_back_whole_when_the_reduced_program_does_not_fit(monkeypatch):
     """a block compiled with merged row tiles whose REDUCED program does not fit the input-stationary kernel (after the complete one uploaded) falls back to the
     plain programs as a whole: nothing merged stays in the table, the recorded merge groups are empty (so no plain twins, and refresh() tags what is uploaded)"""

@@ -360,6 +360,21 @@ def test_device_repack_equals_recompile(kw):
     assert r["inference_rel_diff"] < G.SAME_MATH_TOL and r["step_moved_H"] > 1e-3, r      # inference -> step -> inference: no stale cached chain
 
 
+@pytest.mark.parametrize("kw", [dict(use_corr_prod=True), dict(transformer=True)], ids=["conv_corr_prod", "transformer"])
+def test_weight_lifecycle_of_the_node_level_modules(kw):
+    """the GPU twin of the CPU case of this name: refresh == recompile on a backbone with CorrProductBlocks, the sticky row-program flag and
+    training.enable_row_programs, and no attribute born after construction on any module or uploaded table"""
+    r = G.check_refresh_equals_recompile(lifecycle=True, **kw)
+    print(r)
+    assert r["packers"] >= 8 and r["loss_rel_diff"] < 1e-6 and r["grad_max_rel_diff"] < 1e-5, r
+    assert r["inference_rel_diff"] < 1e-6 and r["step_moved_H"] > 1e-3, r
+    assert r["rowprogs_while_training"] == 0, r
+    assert r["enabled_rel_diff"] < 1e-6 and r["enabled_ham_rowprogs"] >= 1, r
+    if "transformer" not in kw:                                # (an AttentionBlockE3 runs its ResidualBlock stage by stage: only ConvBlockE3's holds a fused chain)
+        assert r["enabled_residual_rowprogs"] >= 1, r
+    assert r["attributes_changed"] == {} and r["objects_watched"] > 100, r
+
+
 def test_full_model_training_loss_falls():
     r = G.check_full_training()
     print(r)
