@@ -16,8 +16,8 @@ class Graph(dict):
         self[k] = v
 
     def to(self, device, non_blocking=False):
-        # the topology cache (hamgnn_amd/topo.py) belongs to THIS object's tensors: never copied to a derived graph
-        return Graph({k: (v.to(device, non_blocking=non_blocking) if torch.is_tensor(v) else v) for k, v in self.items() if k != "_hg_topology"})
+        # the topology cache (hamgnn_amd/topo.py) and the internal graph (hamgnn_amd/internal_graph.py) belong to THIS object's tensors: never copied to a derived graph
+        return Graph({k: (v.to(device, non_blocking=non_blocking) if torch.is_tensor(v) else v) for k, v in self.items() if k not in ("_hg_topology", "_hg_internal_graph")})
 
     def to_dict(self):
         return dict(self)

@@ -17,7 +17,9 @@ class CapturedForward:
     def __init__(self, fn, warmup: int = 2, fine_split: bool = True):
         """fine_split=False: the captured launches are the eager ones -- replays are then bit-identical to eager forwards and to each other; the default spreads the
         smallest crystals' edge launches finer (one workgroup per (segment, share of its phases), tiles ADDED with hardware atomics: the one schedule of this
-        library without a fixed summation order, results within fp32 rounding of the eager ones)"""
+        library without a fixed summation order, results within fp32 rounding of the eager ones).
+        A backbone with HamGNN_pre.build_internal_graph: the internal graph is built (with its host read-backs) during the warm-up forwards and cached on the data
+        object; the capture records the launches on THAT graph, so a replay uses the internal graph as it was at capture time -- capture again after the positions change"""
         if not torch.cuda.is_available():
             raise RuntimeError("CapturedForward needs a GPU: HIP graphs replay device work")
         from . import ops

@@ -15,6 +15,7 @@ from .. import nn as hnn
 from .. import ops
 from .. import parallel
 from .. import plan as P
+from ..internal_graph import check_radius_config, get_internal_graph, restrict_geometry
 from ..so3 import Irreps
 from ..topo import get_topology, gget
 
@@ -101,8 +102,15 @@ class _BackboneBase(hnn.CompiledModule, nn.Module):
         if self.rbf_func not in ("bessel", "gaussian"):
             raise ValueError(f"Unsupported radial basis function: {g('rbf_func')}")      # hamgnn_conv.py:139-141
         self.lite_mode = bool(g("lite_mode", False))
-        if g("build_internal_graph", False):
-            raise NotImplementedError("HamGNN_pre.build_internal_graph=True is outside the MI355X hot-path scope of this round (SURVEY 8f)")
+        # build_internal_graph (hamgnn_conv.py:252-283): messages pass on the wider periodic graph of hamgnn_amd/internal_graph.py, rebuilt on the device when the
+        # positions change; the representation goes back on the data's own edges.  radius_scale: hamgnn_conv.py:90-95, read only with the switch on
+        self.build_internal_graph = bool(g("build_internal_graph", False))
+        self._internal = None                                  # the internal graph of the forward under way
+        if self.build_internal_graph:
+            if bool(g("use_kan", False)):
+                raise NotImplementedError("HamGNN_pre.build_internal_graph=True together with use_kan=True is not built")
+            self.radius_type = str(g("radius_type", "openmx"))
+            self.radius_scale = check_radius_config(g("radius_scale"))
         # use_kan: every radial weight generator is a B-spline KAN (message_passing.py:184-185, tensor_products.py:163-164) -- forward only, HamGNNConvE3 only
         self.use_kan = bool(g("use_kan", False))
         if self.use_kan and not self._kan_built:
@@ -196,9 +204,10 @@ class _BackboneBase(hnn.CompiledModule, nn.Module):
             self.compile(dev)
         N = data.z.shape[0]
         z = data.z.contiguous()
-        topo = get_topology(data)                              # index plumbing + validation: once per graph object (host-syncs)
+        graph = self._message_graph(data)                      # build_internal_graph: topology, geometry and radial prefill of the internal graph
+        topo = get_topology(graph)                             # index plumbing + validation: once per graph object (host-syncs)
         topo.check_num_types(self.num_types)                   # z >= num_types would index past the embedding tables on the device
-        geo = ops.Geometry(data.pos, data.edge_index, data.nbr_shift, self.cutoff, self.num_radial, self.lmax, self._jtab, self.rbf_func)
+        geo = ops.Geometry(graph.pos, graph.edge_index, graph.nbr_shift, self.cutoff, self.num_radial, self.lmax, self._jtab, self.rbf_func)
         # hidden activations of ALL radial weight generators of this forward (embedding + two per message block) in one launch
         if self.use_kan:
             ops.prefill_kan_hidden(geo, self._radial_generators())
@@ -219,6 +228,28 @@ class _BackboneBase(hnn.CompiledModule, nn.Module):
             node = (self._chem[z] + delta @ self._chem).contiguous()                # per-atom rows of the same table
         return z, topo, geo, node, f
 
+    def _message_graph(self, data):
+        """the graph the layers pass messages on: `data`, or with build_internal_graph its (cached) internal graph"""
+        self._internal = None
+        if not self.build_internal_graph:
+            return data
+        if parallel.is_sharded(data):
+            raise NotImplementedError("HamGNN_pre.build_internal_graph=True on an edge-sharded or node-sharded graph is not built: "
+                                      "the internal graph is built from the whole crystal")
+        self._internal = get_internal_graph(data, self.radius_type, self.radius_scale)
+        return self._internal
+
+    def _backward_graph(self, data, rep, g_edge_rot):
+        """(graph, geometry, edge-row gradient) the block backwards run on.  build_internal_graph: the internal graph's, with the gradient of the gathered
+        edge rows placed into zeros over the internal edges (matching_edges is injective: every other internal edge row got no gradient from the head)"""
+        ig = rep.get("_internal_graph")
+        if ig is None:
+            return data, rep["_geometry"], g_edge_rot
+        geo = rep["_internal_geometry"]
+        g = torch.zeros(geo.E, g_edge_rot.shape[1], device=g_edge_rot.device, dtype=g_edge_rot.dtype)
+        g.index_copy_(0, ig["matching_edges"], g_edge_rot.contiguous())
+        return ig, geo, g
+
     def _radial_generators(self):
         gens = [self.pair_embedding._h]
         for m in self.modules():
@@ -231,6 +262,16 @@ class _BackboneBase(hnn.CompiledModule, nn.Module):
         edge rows; the public `edge_attr` goes through it, so anything but the declared head sees exactly what the reference returns"""
         rep = Representation()
         imap, rot_tab = self._imap, self._rot_tab
+        ig = self._internal
+        if ig is not None:
+            # build_internal_graph (hamgnn_conv.py:280-281: edge_attr[matching_edges]): the edge rows and the geometry go back on the data's edges, so the head,
+            # the lazy edge_attr and the complete-rows thunk all see E_data rows; node rows are untouched; the internal ones stay for the backward
+            rep["_internal_graph"], rep["_internal_geometry"] = ig, geo
+            rows = ig["matching_edges"]
+            f, geo = f.index_select(0, rows), restrict_geometry(geo, rows)
+            if full_edge_rows is not None:
+                on_internal = full_edge_rows
+                full_edge_rows = lambda: on_internal().index_select(0, rows)
         rep.set_lazy("node_attr", lambda: ops.from_planar(node, imap))
         if full_edge_rows is None:
             rep.set_lazy("edge_attr", lambda: ops.from_planar(ops.rotate_gather(f, None, geo, rot_tab, transpose=True), imap))
@@ -468,9 +509,9 @@ class HamGNNConvE3(_BackboneBase):
         if parallel.is_sharded(data) and self.apply_charge_doping:
             raise NotImplementedError("backbone backward of an edge-sharded graph with charge doping")
         tape = rep["_tape"]
-        geo = rep["_geometry"]
+        graph, geo, g_edge_rot = self._backward_graph(data, rep, g_edge_rot)     # (build_internal_graph: topology and geometry of the internal graph)
         z = data.z.contiguous()
-        topo = get_topology(data)
+        topo = get_topology(graph)
         N = z.shape[0]
         rp_r, pm_r = topo.receiver_csr()
         rp_s, pm_s = topo.sender_csr()

@@ -68,9 +68,10 @@ class HamGNNTransformer(_BackboneBase):
         """as HamGNNConvE3.backward: gradients of every backbone parameter for the gradients of the representation (planar node rows,
         edge-frame edge rows); per layer, last to first: PairInteractionBlock -> CorrProductBlock -> AttentionBlockE3; then the embeddings."""
         from ..topo import get_topology
-        tape, geo = rep["_tape"], rep["_geometry"]
+        tape = rep["_tape"]
+        graph, geo, g_edge_rot = self._backward_graph(data, rep, g_edge_rot)     # (build_internal_graph: topology and geometry of the internal graph)
         z = data.z.contiguous()
-        topo = get_topology(data)
+        topo = get_topology(graph)
         grads = {}
         g_node, g_f = g_node.contiguous(), g_edge_rot.contiguous()
         for li in reversed(range(self.num_layers)):

@@ -1007,3 +1007,66 @@ def sym_contraction(h, z, C, tab, W1, W2, out_dim):
                                    ptr(tab["out_off"]), ptr(tab["ptr1"]), ptr(tab["ent1"]), ptr(tab["ptr2"]), ptr(tab["ent2"]), ptr(W1),
                                    i32(W1.shape[1]), ptr(W2), i32(W2.shape[1]), ptr(out), i64(out_dim), _stream()), "hg_sym_contraction")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ periodic neighbour list (HamGNN_pre.build_internal_graph)
+class CellList:
+    """what hg_neighbour_bin leaves for the pair passes: per-crystal parameters, the bin of every atom and its wrap into the home cell, and (filled by the caller
+    from a sort of bin_id) the atoms in bin order with the first slot of every bin"""
+
+    def __init__(self, cpar, ipar, bin_id, wrap, bins_cap, B):
+        self.cpar, self.ipar, self.bin_id, self.wrap, self.bins_cap, self.B = cpar, ipar, bin_id, wrap, int(bins_cap), int(B)
+        self.bin_atoms = self.bin_start = None
+
+
+@_on_tensor_device
+def neighbour_bin(pos: torch.Tensor, cell: torch.Tensor, batch, atom_ptr: torch.Tensor, rcut: torch.Tensor, flags: torch.Tensor) -> CellList:
+    """hg_neighbour_bin: pos [N, 3] fp32, cell [B, 3, 3] fp32, batch [N] int64 or None (one crystal), atom_ptr [B + 1] int64, rcut: fp64 device scalar (the largest
+    r_i + r_j), flags: int32 device error word"""
+    _require_gpu(pos)
+    N, B = int(pos.shape[0]), int(cell.shape[0])
+    assert pos.dtype == torch.float32 and cell.dtype == torch.float32 and rcut.dtype == torch.float64 and flags.dtype == torch.int32 and atom_ptr.dtype == torch.int64
+    assert batch is None or (batch.dtype == torch.int64 and batch.shape[0] == N)
+    assert pos.is_contiguous() and cell.is_contiguous() and tuple(cell.shape[1:]) == (3, 3) and atom_ptr.shape[0] == B + 1
+    dev = pos.device
+    bins_cap = N + 27 * B
+    cl = CellList(torch.empty(B, 20, device=dev, dtype=torch.float64), torch.empty(B, 8, device=dev, dtype=torch.int32), torch.empty(N, device=dev, dtype=torch.int64),
+                  torch.empty(N, 3, device=dev, dtype=torch.int32), bins_cap, B)
+    check(lib().hg_neighbour_bin(ptr(pos), ptr(cell), ptr(batch), ptr(atom_ptr), ptr(rcut), i64(N), i32(B), i64(bins_cap), ptr(cl.cpar), ptr(cl.ipar), ptr(cl.bin_id),
+                                 ptr(cl.wrap), ptr(flags), _stream()), "hg_neighbour_bin")
+    return cl
+
+
+@_on_tensor_device
+def neighbour_pairs(pos: torch.Tensor, radius: torch.Tensor, batch, cl: CellList, flags: torch.Tensor, seg_ptr=None, capacity: int = 0) -> torch.Tensor:
+    """hg_neighbour_pairs: seg_ptr None -> the count pass, edges per centre [N] int64; else the fill pass, one packed key per edge [capacity] int64 (centre i's in
+    seg_ptr[i] .. seg_ptr[i + 1], unordered inside)"""
+    _require_gpu(pos)
+    N = int(pos.shape[0])
+    assert radius.dtype == torch.float64 and radius.shape[0] == N and radius.is_contiguous()
+    assert cl.bin_atoms.dtype == torch.int64 and cl.bin_atoms.shape[0] == N and cl.bin_start.dtype == torch.int64 and cl.bin_start.shape[0] == cl.bins_cap + 1
+    if seg_ptr is None:
+        out = torch.empty(N, device=pos.device, dtype=torch.int64)
+        counts, keys = out, None
+    else:
+        assert seg_ptr.dtype == torch.int64 and seg_ptr.shape[0] == N + 1 and seg_ptr.is_contiguous()
+        out = torch.empty(int(capacity), device=pos.device, dtype=torch.int64)
+        counts, keys = None, out
+        if capacity == 0:
+            return out
+    check(lib().hg_neighbour_pairs(ptr(pos), ptr(radius), ptr(batch), ptr(cl.cpar), ptr(cl.ipar), ptr(cl.bin_id), ptr(cl.wrap), ptr(cl.bin_start), ptr(cl.bin_atoms),
+                                   i64(N), i32(cl.B), i64(cl.bins_cap), ptr(seg_ptr), i64(capacity), ptr(counts), ptr(keys), ptr(flags), _stream()), "hg_neighbour_pairs")
+    return out
+
+
+@_on_tensor_device
+def neighbour_decode(keys: torch.Tensor, cell: torch.Tensor, batch, N: int):
+    """hg_neighbour_decode: sorted packed keys -> (edge_index [2, E] int64, cell_shift [E, 3] int64, nbr_shift [E, 3] fp32 = S @ cell in fp64, rounded once)"""
+    _require_gpu(keys)
+    E, dev = int(keys.shape[0]), keys.device
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and cell.dtype == torch.float32 and cell.is_contiguous()
+    ei = torch.empty(2, E, device=dev, dtype=torch.int64)
+    cs = torch.empty(E, 3, device=dev, dtype=torch.int64)
+    ns = torch.empty(E, 3, device=dev, dtype=torch.float32)
+    check(lib().hg_neighbour_decode(ptr(keys), i64(E), ptr(cell), ptr(batch), i64(N), i32(cell.shape[0]), ptr(ei), ptr(cs), ptr(ns), _stream()), "hg_neighbour_decode")
+    return ei, cs, ns

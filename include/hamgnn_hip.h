@@ -251,6 +251,36 @@ int hg_from_planar(const float* xp, int64_t rows, int Dp, const int32_t* map, fl
 int hg_embed_lookup(const float* Ta, const float* Tb, const int64_t* z, const int64_t* idx_a, const int64_t* idx_b,
                     int64_t rows, int T, int Tp, float* out, void* stream);
 
+/* Periodic neighbour list of HamGNN_pre.build_internal_graph (BaseModel.generate_graph, hamgnn/models/base_model.py:237-288: ASE's
+ * neighbour list on the host, every forward) as three device passes.  A batch of B crystals: pos [N][3], cell [B][3][3] (rows = lattice
+ * vectors), batch [N] crystal of an atom (NULL: one crystal), atom_ptr [B + 1] cumulative atom counts, radius [N] fp64.  The list holds every
+ * directed pair (i, j, S) of one crystal with |pos_j + S cell - pos_i| < radius_i + radius_j (formed and compared in fp64, strict; all three
+ * directions periodic), (i, i, 0) excluded, self images S != 0 included.  Each edge is ONE int64 key
+ *     i << 39 | j << 15 | (S0 + 16) << 10 | (S1 + 16) << 5 | (S2 + 16)          (N <= 2^24, |S_d| <= 15)
+ * whose ascending order is the canonical edge order (i, j, S0, S1, S2).  Errors that only the device sees are OR-ed into flags[0] (int32,
+ * zeroed by the caller, read back with the edge count): 1 singular / non-finite cell or cut-off, 2 more than 15 images along a direction,
+ * 4 a table or the key buffer too small (nothing is written past either), 8 non-finite position or batch index out of range.
+ *
+ * hg_neighbour_bin: the cell list.  rcut: DEVICE scalar, the largest radius_i + radius_j of the batch.  Per crystal, direction d gets
+ * floor(height_d / rcut) bins in fractional coordinates -- reduced until the crystal has no more bins than atoms (or 27), so bins_cap =
+ * N + 27 B always suffices -- or, below three bins, one bin and ceil(rcut / height_d) images.  Writes cpar [B][20] fp64 (cell, inverse, rcut)
+ * and ipar [B][8] int32 (bins and images per direction, first bin, bin count) for the other two passes, bin_id [N] (batch-global bin of
+ * an atom) and wrap [N][3] int32 (floor of its fractional coordinates: the atom is binned at pos - wrap cell).
+ * The caller sorts: bin_atoms [N] = atoms ordered by bin_id, bin_start [bins_cap + 1] = first slot of every bin.                          */
+int hg_neighbour_bin(const float* pos, const float* cell, const int64_t* batch, const int64_t* atom_ptr, const double* rcut, int64_t N, int B,
+                     int64_t bins_cap, double* cpar, int32_t* ipar, int64_t* bin_id, int32_t* wrap, int32_t* flags, void* stream);
+/* hg_neighbour_pairs: one thread per centre walks its 3 x 3 x 3 bins (wrap-around = image shift) or the images of a one-bin direction, in a
+ * fixed order.  keys == NULL: COUNT pass, counts [N] = edges of every centre (the caller forms seg_ptr [N + 1] = their prefix sum).
+ * keys != NULL: FILL pass, centre i writes its keys to keys[seg_ptr[i] .. seg_ptr[i + 1]) and never at or past `capacity` (flag 4 if the
+ * two passes disagree or the buffer is short).  The caller sorts `keys` ascending (a centre's segment is complete but not ordered).       */
+int hg_neighbour_pairs(const float* pos, const double* radius, const int64_t* batch, const double* cpar, const int32_t* ipar, const int64_t* bin_id,
+                       const int32_t* wrap, const int64_t* bin_start, const int64_t* bin_atoms, int64_t N, int B, int64_t bins_cap,
+                       const int64_t* seg_ptr, int64_t capacity, int64_t* counts, int64_t* keys, int32_t* flags, void* stream);
+/* hg_neighbour_decode: sorted keys -> edge_index [2][E] (row 0 centre i, row 1 neighbour j), cell_shift [E][3] (int64) and
+ * nbr_shift [E][3] = S @ cell of the centre's crystal, formed in fp64 and rounded once.                                                   */
+int hg_neighbour_decode(const int64_t* keys, int64_t E, const float* cell, const int64_t* batch, int64_t N, int B, int64_t* edge_index,
+                        int64_t* cell_shift, float* nbr_shift, void* stream);
+
 /* Read-out head, stage 1 (hamgnn/models/hamgnn_output.py:851-891 merge_tensor_components + :1056-1096 reorder_matrix;
  * SOC/su2: hamgnn/nn/tensor_decomposition.py:553-603 E3TensorDecomposition.get_H + hamgnn_output.py:3149-3152):
  * coeff: planar rows of the HamLayer output regrouped by (L,p) (rotated frame if wig != NULL -> un-rotated here);
