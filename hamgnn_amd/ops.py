@@ -911,6 +911,49 @@ def hk_assemble_adjoint(G, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_ato
 
 
 @_on_tensor_device
+def mulliken_weights(C_, SC, perm, gptr, wk, Gp):
+    """W [ns, Gp] fp32 from the eigenvector rows C_ and S(k) c rows SC, both [ns, M] complex64: column 0 = wk, column 1 + g = wk * the Mulliken
+    weight of orbital group g (perm / gptr int32), pad columns 0 (see include/hamgnn_hip.h:hg_mulliken_weights); every element is written"""
+    _require_gpu(C_)
+    ns, M = int(C_.shape[0]), int(C_.shape[1])
+    G = int(gptr.shape[0]) - 1
+    if C_.dtype != torch.complex64 or SC.dtype != torch.complex64 or tuple(SC.shape) != (ns, M) or tuple(wk.shape) != (ns,):
+        raise ValueError(f"mulliken_weights: C and SC must be complex64 [{ns}, {M}] and wk [{ns}], got {C_.dtype} {tuple(C_.shape)}, {SC.dtype} {tuple(SC.shape)}, {tuple(wk.shape)}")
+    if perm.dtype != torch.int32 or gptr.dtype != torch.int32 or wk.dtype != torch.float32:
+        raise ValueError("mulliken_weights: perm and gptr must be int32, wk float32")
+    if not (perm.is_contiguous() and gptr.is_contiguous() and wk.is_contiguous()) or perm.dim() != 1 or gptr.dim() != 1 or G < 0:
+        raise ValueError("mulliken_weights: perm, gptr and wk must be contiguous 1-d tensors, gptr with at least one entry")
+    if Gp < 1 + G:
+        raise ValueError(f"mulliken_weights: Gp = {Gp} holds no room for the state weight and {G} groups")
+    W = torch.empty(ns, Gp, device=C_.device, dtype=torch.float32)
+    Cr, SCr = torch.view_as_real(C_.contiguous()), torch.view_as_real(SC.contiguous())
+    check(lib().hg_mulliken_weights(ptr(Cr), ptr(SCr), i64(ns), i32(M), ptr(perm), ptr(gptr),
+                                    i32(G), i32(Gp), ptr(wk), ptr(W), _stream()), "hg_mulliken_weights")
+    return W
+
+
+@_on_tensor_device
+def dos_broaden(eps, W, E0, dE, ne, sigma, D=None, accumulate=False):
+    """D [ne, Gp] fp32 (+)= Gaussians of width sigma around the ASCENDING eps [ns], weighted by W [ns, Gp], on the grid E0 + j dE (see
+    include/hamgnn_hip.h:hg_dos_broaden).  accumulate adds to the given D; otherwise every element of D is written."""
+    _require_gpu(W)
+    ns, Gp = int(W.shape[0]), int(W.shape[1])
+    if eps.dtype != torch.float32 or W.dtype != torch.float32 or tuple(eps.shape) != (ns,):
+        raise ValueError(f"dos_broaden: eps must be float32 [{ns}] and W float32, got {eps.dtype} {tuple(eps.shape)}, {W.dtype}")
+    if not (eps.is_contiguous() and W.is_contiguous()) or W.dim() != 2 or (D is not None and not D.is_contiguous()):
+        raise ValueError("dos_broaden: eps, W and D must be contiguous (a sliced tensor would be read or written with the wrong stride)")
+    if D is None:
+        if accumulate:
+            raise ValueError("dos_broaden: accumulate needs the D to add to")
+        D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
+    elif D.dtype != torch.float32 or tuple(D.shape) != (ne, Gp):
+        raise ValueError(f"dos_broaden: D must be float32 [{ne}, {Gp}], got {D.dtype} {tuple(D.shape)}")
+    check(lib().hg_dos_broaden(ptr(eps), ptr(W), i64(ns), i32(Gp), C.c_double(float(E0)), C.c_double(float(dE)), i32(ne), C.c_double(float(sigma)),
+                               i32(1 if accumulate else 0), ptr(D), _stream()), "hg_dos_broaden")
+    return D
+
+
+@_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""
     _require_gpu(H)

@@ -419,6 +419,30 @@ int hg_attn_logits(const float* K, int64_t k_stride, const int64_t* src, const i
 int hg_attn_aggregate(const float* logits, int H, const float* V, int64_t v_stride, const int64_t* rowptr, const int64_t* perm,
                       const int32_t* head_tab, int64_t N, int Dp, float* out, int64_t out_stride, void* stream);
 
+/* Density of states on a k-grid (hamgnn_amd/dos.py; csrc/spectra.hip): the two steps after the eigen-solver.  Neither uses atomics nor a
+ * claim-order reduction: two launches are bit-identical.  Callers allocate everything (no scratch).
+ *
+ * Mulliken weights of the states of one k-chunk.  C, SC [ns][M] complex64 (re, im): eigenvector rows (state = (k, band), the layout of the
+ * solver's eigenvectors) and S(k) c of the same rows; perm int32[gptr[G]]: the orbitals of group 0, then of group 1, ... (ascending inside a
+ * group), gptr int32[G + 1]; wk [ns]: the k-weight of every row.  W [ns][Gp], Gp >= 1 + G:
+ *   W[s][0] = wk[s] exactly (the total DOS takes the state weight, not a sum of projections);
+ *   W[s][1 + g] = wk[s] * sum_{q in [gptr[g], gptr[g+1])} Re(conj(C[s][perm[q]]) SC[s][perm[q]]), one wave per (s, g): lane l sums entries l, l + 64, ...
+ *   in that order, a butterfly adds the lanes;  W[s][1 + G ..] = 0.  Every element of W is written.
+ * ns <= 0: returns 0 without a launch.  Refused (-2): M <= 0, G < 0, Gp < 1 + G, ns > 2^31 - 1.                                     */
+int hg_mulliken_weights(const float* C, const float* SC, int64_t ns, int M, const int32_t* perm, const int32_t* gptr, int G, int Gp,
+                        const float* wk, float* W, void* stream);
+
+/* Gaussian broadening onto a uniform energy grid: D[j][c] (+)= sum_s A(E0 + j dE, eps[s]) W[s][c],  A(E, e) = exp(-(E - e)^2 / (2 sigma^2)) /
+ * (sigma sqrt(2 pi)).  eps [ns] ASCENDING, W [ns][Gp], D [ne][Gp] fp32; E0, dE, sigma doubles in the unit of eps.  A GEMM whose left operand
+ * is never stored: one workgroup per (tile of 16 energies, slab of 64 columns) finds by binary search the window of states within 6 sigma of
+ * its tile (beyond it a Gaussian is below e^-18 of its peak), generates one Gaussian per lane and step of 4 states in registers (E - eps and
+ * the exponent in double, rounded once) and feeds v_mfma_f32_16x16x4_f32; its 4 waves take contiguous quarters of the window and add their
+ * tiles in a fixed order.  accumulate 0: every element of D is written (0 where the window is empty); 1: added to what D holds (k-chunks in
+ * turn).  ns, ne, Gp need not be multiples of anything.  ne <= 0 or Gp <= 0: returns 0 without a launch.  Refused (-2): sigma <= 0, dE <= 0,
+ * ns < 0 or ns >= 2^31 - 8, Gp > 65535 * 64, W or D not 16-byte aligned.                                                                                         */
+int hg_dos_broaden(const float* eps, const float* W, int64_t ns, int Gp, double E0, double dE, int ne, double sigma, int accumulate,
+                   float* D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
