@@ -1,7 +1,8 @@
-// spectra.hip -- density of states on a k-grid (hamgnn_amd/dos.py): the two steps after the eigen-solver (gfx950).
+// spectra.hip -- density of states on a k-grid (hamgnn_amd/dos.py): the steps after the eigen-solver (gfx950).
 //   hg_mulliken_weights: per-state Mulliken weights of orbital groups, w[s, g] = wk[s] * sum_{mu in g} Re(conj(c_mu) (S c)_mu)
 //   hg_dos_broaden:      D[j, g] = sum_s A(E_j, eps_s) W[s, g], A a normalised Gaussian: a GEMM whose left operand is generated in registers
-// No atomics, no claim-order reduction: both kernels are bit-reproducible from launch to launch.  Callers allocate everything.
+//   hg_dos_tetra:        the same GEMM with the linear tetrahedron method's corner weights (DOS or number of states) as the left operand
+// No atomics, no claim-order reduction: all kernels are bit-reproducible from launch to launch.  Callers allocate everything.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hg_common.h"
@@ -188,4 +189,201 @@ extern "C" int hg_dos_broaden(const float* eps, const float* W, int64_t ns, int 
         dos_broaden_kernel<false><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, (int)ns, Gp, E0, dE, ne, 1.0 / sigma, norm, 6.0 * sigma,
                                                                                             accumulate ? 1 : 0, D);
     return hg_check_launch("hg_dos_broaden");
+}
+
+// ------------------------------------------------------------------------------------------------ linear tetrahedron method
+// The weights (Bloechl, Jepsen, Andersen 1994; the same text stands in hamgnn_amd/dos.py and include/hamgnn_hip.h).  Inside a tetrahedron of weight v
+// the band energy and the projection weight are linear.  Corner energies sorted e1 <= e2 <= e3 <= e4 (ties keep the corner order), e_ij = e_i - e_j,
+// q = v / 4, a = E - e1, b = E - e2, c = e3 - E, d = e4 - E.  Corner weight of the DOS, c_i(E) = g_T(E) * (barycentric coordinate i of the centroid of
+// the cross-section at E), and of the number of states, w_i(E) = integral of c_i up to E:
+//   flat (e4 - e1 < dE): a delta at the mean m of the four: DOS q max(0, 1 - |E - m| / dE) / dE per corner (on the grid: cloud-in-cell between the
+//        two energies that bracket m) if E0 <= m <= E0 + (ne - 1) dE, else 0;  number of states: q per corner where E >= m, else 0;
+//   E <= e1: 0;   E >= e4: 0 (DOS), q per corner (number of states);
+//   e1 < E < e2:  f_j = a / e_j1;  DOS  c_1 = (v f2 f3 / e41) (3 - f2 - f3 - f4), c_j = (v f2 f3 / e41) f_j;
+//                 states  C = q f2 f3 f4:  w_1 = C (4 - f2 - f3 - f4), w_j = C f_j;
+//   e2 <= E < e3: C1 = q a^2 / (e41 e31), C2 = q a b c / (e41 e32 e31), C3 = q b^2 d / (e42 e32 e41);
+//                 w_1 = C1 + (C1 + C2) c / e31 + (C1 + C2 + C3) d / e41,   w_2 = C1 + C2 + C3 + (C2 + C3) c / e32 + C3 d / e42,
+//                 w_3 = (C1 + C2) a / e31 + (C2 + C3) b / e32,             w_4 = (C1 + C2 + C3) a / e41 + C3 b / e42;
+//                 DOS: their derivatives, term by term (C1' = 2 q a / (e41 e31), C2' = q (b c + a c - a b) / (e41 e32 e31), C3' = q (2 b d - b^2) /
+//                 (e42 e32 e41)): no e21 in a denominator, so e1 = e2 forms no 0 / 0;
+//   e3 <= E < e4: h_j = d / e_4j;  DOS  c_4 = (v h1 h2 / e43) (3 - h1 - h2 - h3), c_j = (v h1 h2 / e43) h_j;
+//                 states  C = q h1 h2 h3:  w_4 = q - C (4 - h1 - h2 - h3), w_j = q - C h_j.
+// A branch is entered only where its interval is not empty, so every denominator it uses is positive.  All of it in double from the fp32 eigenvalues.
+__device__ __forceinline__ double tetra_corner(double e1, double e2, double e3, double e4, int r, double E, double v, int mode, double dE, double g_lo,
+                                               double g_hi) {
+    const double q = 0.25 * v;
+    if (e4 - e1 < dE) {
+        const double m = 0.25 * (((e1 + e2) + e3) + e4);
+        if (mode) return E >= m ? q : 0.0;
+        const double t = 1.0 - fabs(E - m) / dE;
+        return (m >= g_lo && m <= g_hi && t > 0.0) ? q * t / dE : 0.0;
+    }
+    if (E <= e1) return 0.0;
+    if (E >= e4) return mode ? q : 0.0;
+    if (E < e2) {
+        const double a = E - e1, f2 = a / (e2 - e1), f3 = a / (e3 - e1), f4 = a / (e4 - e1);
+        const double fr = r == 1 ? f2 : r == 2 ? f3 : f4, pre = mode ? q * f2 * f3 * f4 : v * f2 * f3 / (e4 - e1);
+        return r == 0 ? pre * ((mode ? 4.0 : 3.0) - (f2 + f3 + f4)) : pre * fr;
+    }
+    if (E >= e3) {
+        const double d = e4 - E, h1 = d / (e4 - e1), h2 = d / (e4 - e2), h3 = d / (e4 - e3);
+        const double hr = r == 0 ? h1 : r == 1 ? h2 : h3, pre = mode ? q * h1 * h2 * h3 : v * h1 * h2 / (e4 - e3);
+        const double x = r == 3 ? pre * ((mode ? 4.0 : 3.0) - (h1 + h2 + h3)) : pre * hr;
+        return mode ? q - x : x;
+    }
+    const double a = E - e1, b = E - e2, c = e3 - E, d = e4 - E;
+    const double i31 = 1.0 / (e3 - e1), i41 = 1.0 / (e4 - e1), i32 = 1.0 / (e3 - e2), i42 = 1.0 / (e4 - e2);
+    const double C1 = q * a * a * i41 * i31, C2 = q * a * b * c * i41 * i32 * i31, C3 = q * b * b * d * i42 * i32 * i41;
+    if (mode) {
+        return r == 0 ? C1 + (C1 + C2) * c * i31 + (C1 + C2 + C3) * d * i41
+             : r == 1 ? C1 + C2 + C3 + (C2 + C3) * c * i32 + C3 * d * i42
+             : r == 2 ? (C1 + C2) * a * i31 + (C2 + C3) * b * i32
+                      : (C1 + C2 + C3) * a * i41 + C3 * b * i42;
+    }
+    const double D1 = 2.0 * q * a * i41 * i31, D2 = q * (b * c + a * c - a * b) * i41 * i32 * i31, D3 = q * (2.0 * b * d - b * b) * i42 * i32 * i41;
+    return r == 0 ? D1 + ((D1 + D2) * c - (C1 + C2)) * i31 + ((D1 + D2 + D3) * d - (C1 + C2 + C3)) * i41
+         : r == 1 ? D1 + D2 + D3 + ((D2 + D3) * c - (C2 + C3)) * i32 + (D3 * d - C3) * i42
+         : r == 2 ? ((D1 + D2) * a + (C1 + C2)) * i31 + ((D2 + D3) * b + (C2 + C3)) * i32
+                  : ((D1 + D2 + D3) * a + (C1 + C2 + C3)) * i41 + (D3 * b + C3) * i42;
+}
+
+// One workgroup owns one (tile of 16 energies, slab of 64 columns), as dos_broaden_kernel, and the GEMM runs over the states s = (band, k).  eps ascends
+// in b at every k, so band_lo (min over k) and band_hi (max over k) both ascend in b and the bands that matter to the tile are a contiguous range found
+// by binary search: DOS -- band_hi >= E_first - 2 dE and band_lo <= E_last + 2 dE (a tetrahedron contributes inside [e1, e4], a flat one within dE of
+// its mean; the second dE keeps a rounding of the limit out of the decision); number of states -- band_lo <= E_last, and the bands with band_hi <=
+// E_first are full at every energy of the tile: their element is q * (entries of the k-row) without a look at the eigenvalues.  The states of the range,
+// (b - b_lo) nk + k, are cut into steps of 4 (one v_mfma_f32_16x16x4_f32 each; a step may straddle two bands) dealt to the 4 waves in contiguous
+// quarters.  Per step a lane generates ONE element A[energy lane & 15][state lane >> 4]: it walks the corner table of its k-row in the table's order
+// (ascending tetrahedron: the fixed summation order), per entry loads the tetrahedron's four eigenvalues of band b, sorts them (5 comparators), takes
+// the rank of its own corner (ties: the lower slot first, so repeated corners of a folded or n_i = 1 grid take distinct ranks) and adds tetra_corner
+// in double; the sum is rounded to fp32 once.  The 16 lanes of a state walk the same entries: their loads are one address.  W loads, tails, the
+// LDS reduction ((w0 + w1) + w2) + w3 and the stores are dos_broaden_kernel's.  Table entries are clamped into range before they index anything.
+template <bool VEC>
+__global__ __launch_bounds__(64 * DB_WAVES) void dos_tetra_kernel(const float* __restrict__ eps, const float* __restrict__ W, int nk, int nb, int Gp,
+                                                                  const int4* __restrict__ tet, int nt, const int32_t* __restrict__ kt_ptr,
+                                                                  const int32_t* __restrict__ kt_tet, const int32_t* __restrict__ kt_corner,
+                                                                  const float* __restrict__ band_lo, const float* __restrict__ band_hi, double E0,
+                                                                  double dE, int ne, int mode, int accumulate, float* __restrict__ D) {
+    __shared__ float part[DB_WAVES][DB_NT][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.x * 16, c0 = blockIdx.y * (16 * DB_NT);
+    const int jl = j0 + 15 < ne ? j0 + 15 : ne - 1;
+    auto energy = [&](int j) { return __dadd_rn(E0, __dmul_rn((double)j, dE)); };      // (two roundings, as the host computes the grid: no fma)
+    const double E_first = energy(j0), E_last = energy(jl), g_lo = E0, g_hi = energy(ne - 1);
+    auto first_above = [&](const float* __restrict__ x, double lim, bool strict) {      // first b with x[b] > lim (strict) / >= lim
+        int a = 0, b = nb;
+        while (a < b) {
+            const int m = (a + b) >> 1;
+            if (strict ? (double)x[m] <= lim : (double)x[m] < lim) a = m + 1; else b = m;
+        }
+        return a;
+    };
+    const int b_lo = mode ? 0 : first_above(band_hi, E_first - 2.0 * dE, false);
+    const int b_hi = first_above(band_lo, mode ? E_last : E_last + 2.0 * dE, true);
+    const int b_full = mode ? first_above(band_hi, E_first, true) : 0;                   // bands below it: band_hi <= E_first
+    const int ns = b_hi > b_lo ? (b_hi - b_lo) * nk : 0;                                 // (the host keeps nk nb below 2^31)
+    const int nsteps = (ns + 3) >> 2;
+    if (nsteps == 0 && accumulate) return;                     // (block-uniform) no band in reach leaves D alone
+    const int chunk = (nsteps + DB_WAVES - 1) / DB_WAVES;
+    const int st0 = wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
+    const double Ej = energy(j0 + (lane & 15)), v = 1.0 / (double)nt;
+    const int kq = lane >> 4, col = c0 + DB_NT * (lane & 15);
+    const int colc = VEC ? (col < Gp ? col : Gp - DB_NT) : 0;
+    f32x4 acc[DB_NT];
+#pragma unroll
+    for (int t = 0; t < DB_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int st = st0; st < st1; ++st) {                       // (wave-uniform bounds; st0 < st1 implies ns > 0)
+        const int s_raw = 4 * st + kq, s = s_raw < ns ? s_raw : ns - 1;
+        const int bb = s / nk, k = s - bb * nk, b = b_lo + bb;
+        const float* __restrict__ w = W + ((int64_t)k * nb + b) * Gp;
+        float bv[DB_NT];
+        if (VEC) {
+            const float4 x = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w + colc, 16));
+            bv[0] = x.x, bv[1] = x.y, bv[2] = x.z, bv[3] = x.w;
+        } else {
+#pragma unroll
+            for (int t = 0; t < DB_NT; ++t) bv[t] = w[col + t < Gp ? col + t : Gp - 1];
+        }
+        const int q0 = kt_ptr[k] > 0 ? kt_ptr[k] : 0, q1 = kt_ptr[k + 1] < 4 * nt ? kt_ptr[k + 1] : 4 * nt;
+        double A = 0.0;
+        if (b < b_full) {
+            A = (double)(q1 - q0) * (0.25 * v);
+        } else {
+            for (int q = q0; q < q1; ++q) {
+                int T = kt_tet[q];
+                T = T < 0 ? 0 : T < nt ? T : nt - 1;
+                const int slot = kt_corner[q] & 3;
+                const int4 cn = tet[T];
+                auto ev = [&](int kk) { kk = kk < 0 ? 0 : kk < nk ? kk : nk - 1; return (double)eps[(int64_t)kk * nb + b]; };
+                double x0 = ev(cn.x), x1 = ev(cn.y), x2 = ev(cn.z), x3 = ev(cn.w);
+                const double me = slot == 0 ? x0 : slot == 1 ? x1 : slot == 2 ? x2 : x3;
+                const int r = (int)(x0 < me || (x0 == me && 0 < slot)) + (int)(x1 < me || (x1 == me && 1 < slot)) +
+                              (int)(x2 < me || (x2 == me && 2 < slot)) + (int)(x3 < me);
+                double t;
+#define HG_CSWAP(p, q_) t = fmin(p, q_), q_ = fmax(p, q_), p = t
+                HG_CSWAP(x0, x1); HG_CSWAP(x2, x3); HG_CSWAP(x0, x2); HG_CSWAP(x1, x3); HG_CSWAP(x1, x2);
+#undef HG_CSWAP
+                A += tetra_corner(x0, x1, x2, x3, r, Ej, v, mode, dE, g_lo, g_hi);
+            }
+        }
+        const float av = s_raw < ns ? (float)A : 0.f;
+#pragma unroll
+        for (int t = 0; t < DB_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[t], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < DB_NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[wave][t][r][lane] = acc[t][r];
+    __syncthreads();
+    {                                                          // C/D map of a 16x16 tile: MFMA column = lane & 15, row = 4 (lane >> 4) + r; wave w adds and stores rows r = w
+        const int r = wave, row = j0 + 4 * kq + r;
+        float o[DB_NT];
+#pragma unroll
+        for (int t = 0; t < DB_NT; ++t) {
+            o[t] = part[0][t][r][lane];
+#pragma unroll
+            for (int w2 = 1; w2 < DB_WAVES; ++w2) o[t] += part[w2][t][r][lane];
+        }
+        if (row < ne) {
+            float* dst = D + (int64_t)row * Gp + col;
+            if (VEC) {
+                if (col < Gp) {
+                    float4 x = make_float4(o[0], o[1], o[2], o[3]);
+                    if (accumulate) {
+                        const float4 old = *reinterpret_cast<const float4*>(dst);
+                        x = make_float4(old.x + x.x, old.y + x.y, old.z + x.z, old.w + x.w);
+                    }
+                    *reinterpret_cast<float4*>(dst) = x;
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < DB_NT; ++t)
+                    if (col + t < Gp) dst[t] = accumulate ? dst[t] + o[t] : o[t];
+            }
+        }
+    }
+}
+
+extern "C" int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, int Gp, const int32_t* tet, int64_t nt, const int32_t* kt_ptr,
+                            const int32_t* kt_tet, const int32_t* kt_corner, const float* band_lo, const float* band_hi, double E0, double dE, int ne,
+                            int mode, int accumulate, float* D, void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (ne <= 0) return 0;
+    if (!(dE > 0.0) || (mode != 0 && mode != 1) || nt < 0 || nt > 2147483647LL / 4 || Gp < 1 || nk < 0 || nb < 0 ||
+        (int64_t)nk * nb > 2147483647LL - 8)
+        return hg_fail(-2, "hg_dos_tetra: bad arguments (dE must be positive, mode 0 or 1, nt >= 0, Gp >= 1, nk nb < 2^31)");
+    const bool states = nk > 0 && nb > 0 && nt > 0;            // without states every element of D is 0 (or left alone)
+    if (!D || (states && (!eps || !W || !tet || !kt_ptr || !kt_tet || !kt_corner || !band_lo || !band_hi)))
+        return hg_fail(-2, "hg_dos_tetra: null pointer");
+    if ((((uintptr_t)W | (uintptr_t)D | (uintptr_t)tet) & 15)) return hg_fail(-2, "hg_dos_tetra: W, D and tet must be 16-byte aligned");
+    const unsigned gx = (unsigned)((ne + 15) / 16), gy = (unsigned)((Gp + 16 * DB_NT - 1) / (16 * DB_NT));
+    if (gy > 65535u) return hg_fail(-2, "hg_dos_tetra: too many group columns");
+    const int nbe = states ? nb : 0;                           // no band in reach of any tile: zeros written / D left alone, nothing read
+    if ((Gp & 3) == 0)
+        dos_tetra_kernel<true><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner,
+                                                                                         band_lo, band_hi, E0, dE, ne, mode, accumulate ? 1 : 0, D);
+    else
+        dos_tetra_kernel<false><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner,
+                                                                                          band_lo, band_hi, E0, dE, ne, mode, accumulate ? 1 : 0, D);
+    return hg_check_launch("hg_dos_tetra");
 }

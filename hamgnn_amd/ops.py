@@ -954,6 +954,40 @@ def dos_broaden(eps, W, E0, dE, ne, sigma, D=None, accumulate=False):
 
 
 @_on_tensor_device
+def dos_tetra(eps, W, tet, kt, band_lo, band_hi, E0, dE, ne, mode=0, D=None, accumulate=False):
+    """D [ne, Gp] fp32 (+)= the linear tetrahedron method's DOS (mode 0) or number of states (mode 1) on the grid E0 + j dE: eps [nk, nb] ascending in b,
+    W [nk, nb, Gp], tet int32 [nt, 4], kt = (kt_ptr [nk + 1], kt_tet [4 nt], kt_corner [4 nt]) int32 (dos.corner_table), band_lo / band_hi [nb] = min / max
+    of eps over k (see include/hamgnn_hip.h:hg_dos_tetra).  accumulate adds to the given D; otherwise every element of D is written."""
+    _require_gpu(W)
+    if W.dim() != 3 or eps.dim() != 2 or tet.dim() != 2 or len(kt) != 3:
+        raise ValueError(f"dos_tetra: eps must be [nk, nb], W [nk, nb, Gp], tet [nt, 4] and kt three tensors, got {tuple(eps.shape)}, {tuple(W.shape)}, {tuple(tet.shape)}")
+    nk, nb, Gp = (int(v) for v in W.shape)
+    nt = int(tet.shape[0])
+    kt_ptr, kt_tet, kt_corner = kt
+    f32s, i32s = (eps, W, band_lo, band_hi), (tet, kt_ptr, kt_tet, kt_corner)
+    if any(t.dtype != torch.float32 for t in f32s) or any(t.dtype != torch.int32 for t in i32s):
+        raise ValueError("dos_tetra: eps, W, band_lo and band_hi must be float32, tet and the corner table int32")
+    if not all(t.is_contiguous() for t in f32s + i32s) or (D is not None and not D.is_contiguous()):
+        raise ValueError("dos_tetra: eps, W, tet, the corner table, band_lo, band_hi and D must be contiguous (a sliced tensor would be read or written with the wrong stride)")
+    if (tuple(eps.shape) != (nk, nb) or tuple(tet.shape) != (nt, 4) or tuple(kt_ptr.shape) != (nk + 1,) or tuple(kt_tet.shape) != (4 * nt,)
+            or tuple(kt_corner.shape) != (4 * nt,) or tuple(band_lo.shape) != (nb,) or tuple(band_hi.shape) != (nb,)):
+        raise ValueError(f"dos_tetra: shapes do not fit nk = {nk}, nb = {nb}, nt = {nt}: eps {tuple(eps.shape)}, tet {tuple(tet.shape)}, kt_ptr {tuple(kt_ptr.shape)}, "
+                         f"kt_tet {tuple(kt_tet.shape)}, kt_corner {tuple(kt_corner.shape)}, band_lo {tuple(band_lo.shape)}, band_hi {tuple(band_hi.shape)}")
+    if Gp < 1 or mode not in (0, 1):
+        raise ValueError(f"dos_tetra: Gp = {Gp} must be at least 1 and mode = {mode!r} 0 (DOS) or 1 (number of states)")
+    if D is None:
+        if accumulate:
+            raise ValueError("dos_tetra: accumulate needs the D to add to")
+        D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
+    elif D.dtype != torch.float32 or tuple(D.shape) != (ne, Gp):
+        raise ValueError(f"dos_tetra: D must be float32 [{ne}, {Gp}], got {D.dtype} {tuple(D.shape)}")
+    check(lib().hg_dos_tetra(ptr(eps), ptr(W), i32(nk), i32(nb), i32(Gp), ptr(tet), i64(nt), ptr(kt_ptr), ptr(kt_tet), ptr(kt_corner), ptr(band_lo),
+                             ptr(band_hi), C.c_double(float(E0)), C.c_double(float(dE)), i32(ne), i32(mode), i32(1 if accumulate else 0), ptr(D),
+                             _stream()), "hg_dos_tetra")
+    return D
+
+
+@_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""
     _require_gpu(H)

@@ -443,6 +443,30 @@ int hg_mulliken_weights(const float* C, const float* SC, int64_t ns, int M, cons
 int hg_dos_broaden(const float* eps, const float* W, int64_t ns, int Gp, double E0, double dE, int ne, double sigma, int accumulate,
                    float* D, void* stream);
 
+/* Linear tetrahedron method (Bloechl, Jepsen, Andersen 1994) on the same energy grid: D[j][c] (+)= sum_{k,b} A(E0 + j dE; k, b) W[k][b][c],
+ * A(E; k, b) = sum over the entries (T, i) of the corner table of k-row k of the weight of corner i of tetrahedron T at E for band b: mode 0 the
+ * corner-resolved DOS, mode 1 the corner-resolved number of states.  eps [nk][nb] fp32 ASCENDING in b at every k, W [nk][nb][Gp] (the Mulliken rows
+ * of state (k, b) with wk = 1), tet int32[nt][4]: k-rows of the corners of nt tetrahedra of equal weight v = 1 / nt, kt_ptr int32[nk + 1], kt_tet,
+ * kt_corner int32[4 nt]: per k-row the (tetrahedron, corner slot) pairs that touch it, ascending in the tetrahedron -- the fixed summation order;
+ * band_lo, band_hi [nb]: min / max of eps over k (both ascend in b: a tile of 16 energies finds its bands by binary search).
+ * The weights, corner energies sorted e1 <= e2 <= e3 <= e4 (ties: the lower slot first), e_ij = e_i - e_j, q = v / 4, a = E - e1, b = E - e2,
+ * c = e3 - E, d = e4 - E; DOS c_i = g_T(E) x barycentric coordinate i of the centroid of the cross-section at E, number of states w_i = its integral:
+ *   flat, e4 - e1 < dE: a delta at the mean m of the four.  DOS: q max(0, 1 - |E - m| / dE) / dE per corner if E0 <= m <= E0 + (ne - 1) dE (cloud-in-
+ *         cell between the two grid energies that bracket m), else 0.  Number of states: q per corner where E >= m, else 0.
+ *   E <= e1: 0.  E >= e4: DOS 0, number of states q per corner.
+ *   e1 < E < e2:  f_j = a / e_j1, P = v f2 f3 / e41: c_1 = P (3 - f2 - f3 - f4), c_j = P f_j;  C = q f2 f3 f4: w_1 = C (4 - f2 - f3 - f4), w_j = C f_j.
+ *   e2 <= E < e3: C1 = q a^2 / (e41 e31), C2 = q a b c / (e41 e32 e31), C3 = q b^2 d / (e42 e32 e41);
+ *         w_1 = C1 + (C1 + C2) c / e31 + (C1 + C2 + C3) d / e41,  w_2 = C1 + C2 + C3 + (C2 + C3) c / e32 + C3 d / e42,
+ *         w_3 = (C1 + C2) a / e31 + (C2 + C3) b / e32,            w_4 = (C1 + C2 + C3) a / e41 + C3 b / e42;  c_i = d w_i / dE term by term.
+ *   e3 <= E < e4: h_j = d / e_4j, P = v h1 h2 / e43: c_4 = P (3 - h1 - h2 - h3), c_j = P h_j;  C = q h1 h2 h3: w_4 = q - C (4 - h1 - h2 - h3), w_j = q - C h_j.
+ * Evaluated in double from the fp32 eigenvalues, summed over a k-row's entries in double, rounded to fp32 once, accumulated in fp32 on
+ * v_mfma_f32_16x16x4_f32; no atomics: two launches are bit-identical.  accumulate 0: every element of D is written; 1: added to what D holds
+ * (band chunks in turn, all k-points of a chunk at once).  ne <= 0: returns 0 without a launch.  Refused (-2): dE <= 0, mode not 0 / 1, nt < 0 or
+ * > 2^29, Gp < 1 or > 65535 * 64, nk or nb < 0, nk nb >= 2^31 - 8, a null pointer where the sizes are not empty, W, D or tet not 16-byte aligned.  */
+int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, int Gp, const int32_t* tet, int64_t nt, const int32_t* kt_ptr,
+                 const int32_t* kt_tet, const int32_t* kt_corner, const float* band_lo, const float* band_hi, double E0, double dE, int ne,
+                 int mode, int accumulate, float* D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
