@@ -1,5 +1,5 @@
 """Backward of the nu = 3 term of the MACE symmetric contraction (CorrProductBlock with `correlation: 3`; reference:
-hamgnn/toolbox/mace/modules/symmetric_contraction.py:101-233, tools/cg.py:16-131).  Forward (hg_sym_contraction3, csrc/corr3.hip):
+hamgnn/toolbox/mace/modules/symmetric_contraction.py:101-233, tools/cg.py:16-131).  Forward (hg_sym_contraction3, csrc/sym_contraction.hip):
 
     out[n, o, c] += sum_{(x, i, j, kap, v) in ent3[o]} v W3[z_n, kap, c] h[n, x, c] h[n, i, c] h[n, j, c]
 

@@ -11,12 +11,9 @@
 //   hg_attn_aggregate  one workgroup per receiver node: soft-max statistics of its <= few hundred incoming logits in LDS, then ONE pass
 //                      over the value rows V[e, :] (the [E, Dp] output of the fused value MessagePackBlock -- the bytes that matter:
 //                      Dp * 4 B per edge, read exactly once, float4 per thread, four rows in flight), fixed summation order.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
+#include "hg_device.h"
 
 #define AT_MAXH 8
-typedef float at_f4 __attribute__((ext_vector_type(4)));
 
 // exp(-1/x) for x > 0, else 0 (e3nn.math.soft_unit_step), x = cut_param * (1 - r / r_cut)  (hamgnn/utils/cutoff_functions.py:65-100)
 __device__ __forceinline__ float at_soft_cut(float r, float cut_param, float cutoff) {
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(256) void attn_logits_kernel(const float* __restric
 #pragma unroll
         for (int h = 0; h < AT_MAXH; ++h) acc[h] = 0.f;
         for (int p = 4 * lane; p < Dp; p += 256) {
-            const at_f4 va = *reinterpret_cast<const at_f4*>(a + p), vb = *reinterpret_cast<const at_f4*>(b + p);
+            const f32x4 va = *reinterpret_cast<const f32x4*>(a + p), vb = *reinterpret_cast<const f32x4*>(b + p);
             const int4 hd = *reinterpret_cast<const int4*>(head_tab + p);
             const int hh[4] = {hd.x, hd.y, hd.z, hd.w};
 #pragma unroll
@@ -110,7 +107,7 @@ __global__ __launch_bounds__(256) void attn_aggregate_kernel(const float* __rest
             const int4 hd = *reinterpret_cast<const int4*>(head_tab + p);
             hc[0] = hd.x < 0 ? AT_MAXH : hd.x, hc[1] = hd.y < 0 ? AT_MAXH : hd.y, hc[2] = hd.z < 0 ? AT_MAXH : hd.z, hc[3] = hd.w < 0 ? AT_MAXH : hd.w;
         }
-        at_f4 acc = (at_f4){0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int64_t c0 = q0; c0 < q1; c0 += AT_CH) {
             const int nc = (int)((q1 - c0) < AT_CH ? (q1 - c0) : AT_CH);
             __syncthreads();                                   // previous chunk fully consumed
@@ -124,8 +121,8 @@ __global__ __launch_bounds__(256) void attn_aggregate_kernel(const float* __rest
                 const float* __restrict__ vp = V + p;
                 int qi = 0;
                 for (; qi + 4 <= nc; qi += 4) {
-                    const at_f4 v0 = *reinterpret_cast<const at_f4*>(vp + s_e[qi] * vs), v1 = *reinterpret_cast<const at_f4*>(vp + s_e[qi + 1] * vs);
-                    const at_f4 v2 = *reinterpret_cast<const at_f4*>(vp + s_e[qi + 2] * vs), v3 = *reinterpret_cast<const at_f4*>(vp + s_e[qi + 3] * vs);
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(vp + s_e[qi] * vs), v1 = *reinterpret_cast<const f32x4*>(vp + s_e[qi + 1] * vs);
+                    const f32x4 v2 = *reinterpret_cast<const f32x4*>(vp + s_e[qi + 2] * vs), v3 = *reinterpret_cast<const f32x4*>(vp + s_e[qi + 3] * vs);
                     const float* __restrict__ w = s_w + qi * AT_WS;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -136,14 +133,14 @@ __global__ __launch_bounds__(256) void attn_aggregate_kernel(const float* __rest
                     }
                 }
                 for (; qi < nc; ++qi) {
-                    const at_f4 v0 = *reinterpret_cast<const at_f4*>(vp + s_e[qi] * vs);
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(vp + s_e[qi] * vs);
                     const float* __restrict__ w = s_w + qi * AT_WS;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[j] = fmaf(w[hc[j]], v0[j], acc[j]);
                 }
             }
         }
-        if (active) *reinterpret_cast<at_f4*>(out + n * os + p) = acc;
+        if (active) *reinterpret_cast<f32x4*>(out + n * os + p) = acc;
     }
 }
 

@@ -1,14 +1,12 @@
 // block_gemm.hip -- many SMALL independent matrix products in one launch:  C_u = scale_u * op(A_u) @ op(B_u)  for the units of a table.
 // What it replaces: the per-irrep products of a MessagePackBlock's two trailing Linears, L'_k = linear_scaler_k @ linear_out_k / sqrt(mul_k)
-// (/root/reference/hamgnn/nn/message_passing.py:122-130, tensor_products.py:118-140: the reference applies the two Linears one after the other),
+// (hamgnn/nn/message_passing.py:122-130, tensor_products.py:118-140: the reference applies the two Linears one after the other),
 // evaluated once per optimiser step by the device-side repack (hamgnn_amd/repack.py:mp_sources) and, transposed, by the backward of those two
 // Linears (hamgnn_amd/backward_mp.py:TPWeightGrad.finish) -- 13 output irreps x 2 branches x 7 blocks = 182 (repack) + 364 (backward) library GEMMs
 // of [<= 832, <= 64] x [<= 64, <= 64] per training step, each a launch of a few microseconds.  fp32 operands, fp64 accumulation (the host
 // packer rounds once, from float64), fp32 or fp64 result.  Plain FMA on an LDS-tiled 64 x 64 output tile per workgroup: these are kFLOP-sized.
 // Hand-written HIP for gfx950 (CDNA4).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
+#include "hg_device.h"
 
 #define BG_UNIT_I32 12           // {a_off, a_ld, a_trans, b_off, b_ld, b_trans, c_off, c_ld, M, N, K, scale (float bits)}
 #define BG_T 64                  // output tile

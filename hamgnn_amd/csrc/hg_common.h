@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hamgnn_hip.h"                          // every unit sees the public prototypes: a definition that drifts from them does not compile
 
 int hg_fail(int code, const char* msg);          // records msg for hg_last_error(), returns code
 int hg_check_launch(const char* what);           // hipGetLastError() after a launch -> 0 / negative

@@ -10,11 +10,7 @@
 //   knot table row (one input feature, KS = 4 (G + 7) - 6):  t_0 .. t_{G+6} | r1_j = 1 / (t_{j+1} - t_j) | r2_j = 1 / (t_{j+2} - t_j) | r3_j = 1 / (t_{j+3} - t_j)
 //   W'_l  plain  : [(1 + nb) d_l][d_{l+1}] row-major, row p d_l + i = plane p of input i   (p = 0: base_weight, p >= 1: spline_weight[.., p - 1] * spline_scaler)
 //         packed : MFMA A fragments [T][p][rt][lane][4]: lane (i = lane & 15, g = lane >> 4), register q <- W'[p][in = 16 T + 4 g + q][out = 16 rt + i]
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-
-typedef float kan_f4 __attribute__((ext_vector_type(4)));
+#include "hg_device.h"
 
 // phi of one value: out[0] = silu(x), out[1 + j] = B_j(x).  kt: the feature's knot table row (LDS or global).
 template <int G>
@@ -123,16 +119,16 @@ __global__ __launch_bounds__(256) void kan_plain_kernel(const float* __restrict_
 #define KAN_KT (64 * KAN_KS)
 #define KAN_STRIDE (3 * KAN_KT + 2 * KAN_W)
 
-__device__ __forceinline__ void kan_mfma_layer(const kan_f4 (&x)[KAN_NT][4], const float* __restrict__ kn, const kan_f4* __restrict__ frag, int lane, int g,
-                                               kan_f4 (&acc)[KAN_NT][4]) {
+__device__ __forceinline__ void kan_mfma_layer(const f32x4 (&x)[KAN_NT][4], const float* __restrict__ kn, const f32x4* __restrict__ frag, int lane, int g,
+                                               f32x4 (&acc)[KAN_NT][4]) {
 #pragma unroll
     for (int n = 0; n < KAN_NT; ++n)
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[n][rt] = (kan_f4){0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) acc[n][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int T = 0; T < 4; ++T) {
         // (the fragments do not depend on the tile: left alone, the compiler hoists all 224 loads of both layers out of the persistent loop and spills them)
-        const kan_f4* fT = frag + T * (KAN_NP * 4 * 64) + lane;
+        const f32x4* fT = frag + T * (KAN_NP * 4 * 64) + lane;
         asm volatile("" : "+v"(fT));
         float ph[KAN_NT][4][KAN_NP];
 #pragma unroll
@@ -145,7 +141,7 @@ __device__ __forceinline__ void kan_mfma_layer(const kan_f4 (&x)[KAN_NT][4], con
         for (int p = 0; p < KAN_NP; ++p)
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt) {
-                const kan_f4 a = fT[(p * 4 + rt) * 64];
+                const f32x4 a = fT[(p * 4 + rt) * 64];
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -164,19 +160,19 @@ __global__ __launch_bounds__(256) void kan_mfma_kernel(const float* __restrict__
         kn[2 * KAN_KT + idx] = blob[2 * KAN_KT + 2 * KAN_W + idx];
     }
     __syncthreads();
-    const kan_f4* __restrict__ f0 = reinterpret_cast<const kan_f4*>(blob + KAN_KT);
-    const kan_f4* __restrict__ f1 = reinterpret_cast<const kan_f4*>(blob + 2 * KAN_KT + KAN_W);
+    const f32x4* __restrict__ f0 = reinterpret_cast<const f32x4*>(blob + KAN_KT);
+    const f32x4* __restrict__ f1 = reinterpret_cast<const f32x4*>(blob + 2 * KAN_KT + KAN_W);
     const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
     const int64_t ngrp = (E + 16 * KAN_NT - 1) / (16 * KAN_NT);
     for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < ngrp; t += (int64_t)gridDim.x * 4) {
         int64_t e[KAN_NT];
-        kan_f4 x[KAN_NT][4], h1[KAN_NT][4], h2[KAN_NT][4];
+        f32x4 x[KAN_NT][4], h1[KAN_NT][4], h2[KAN_NT][4];
 #pragma unroll
         for (int n = 0; n < KAN_NT; ++n) {
             e[n] = (t * KAN_NT + n) * 16 + i;
             const int64_t er = e[n] < E ? e[n] : E - 1;        // a missing edge reads the last one (never stored)
 #pragma unroll
-            for (int T = 0; T < 4; ++T) x[n][T] = *reinterpret_cast<const kan_f4*>(rbf + er * 64 + 16 * T + 4 * g);
+            for (int T = 0; T < 4; ++T) x[n][T] = *reinterpret_cast<const f32x4*>(rbf + er * 64 + 16 * T + 4 * g);
         }
         kan_mfma_layer(x, kn, f0, lane, g, h1);
         kan_mfma_layer(h1, kn + KAN_KT, f1, lane, g, h2);
@@ -194,7 +190,7 @@ __global__ __launch_bounds__(256) void kan_mfma_kernel(const float* __restrict__
                 if (e[n] < E) {
 #pragma unroll
                     for (int p = 0; p < KAN_NP; ++p)
-                        *reinterpret_cast<kan_f4*>(out + e[n] * (KAN_NP * 64) + p * 64 + 16 * rt + 4 * g) = (kan_f4){ph[n][0][p], ph[n][1][p], ph[n][2][p], ph[n][3][p]};
+                        *reinterpret_cast<f32x4*>(out + e[n] * (KAN_NP * 64) + p * 64 + 16 * rt + 4 * g) = (f32x4){ph[n][0][p], ph[n][1][p], ph[n][2][p], ph[n][3][p]};
                 }
         }
     }

@@ -14,11 +14,8 @@
 // roofline: with all loads served from cache and the stores dropped it still takes 2.1 ms -- 37 MFMAs per unit against ~470 other
 // VALU instructions (64-bit addressing, predicates) and a three-deep scalar table chain per unit at two waves per SIMD.  The next
 // step is rows staged whole through LDS by a workgroup (contiguous 3.5 KB reads, 32-bit LDS addressing); not built.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
+#include "hg_device.h"
 
-typedef float ln_f4 __attribute__((ext_vector_type(4)));
 #ifndef LN_TPW
 #define LN_TPW 2                  // 16-row tiles a wave works on at once (measured: 1 -> 3.9 / 4.5 ms, 2 -> 3.3 / 4.1, 4 -> 3.4 / 4.9)
 #endif
@@ -52,26 +49,26 @@ __global__ __launch_bounds__(256) void linear_planar_kernel(const LinArgs A, con
     // LN_TPW tiles of 16 rows at once: their input float4s are requested together and every weight fragment is loaded once for all
     int64_t row[LN_TPW];
     bool valid[LN_TPW];
-    ln_f4 acc[LN_TPW][4];
+    f32x4 acc[LN_TPW][4];
 #pragma unroll
     for (int t = 0; t < LN_TPW; ++t) {
         const int64_t r = r0 + 16 * t + n;
         valid[t] = r < A.rows;
         row[t] = valid[t] ? r : A.rows - 1;
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[t][rt] = (ln_f4){0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < 4; ++rt) acc[t][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     for (int p = pb; p < pe; ++p) {
         const int* __restrict__ Pp = g_paths + p * 4;
         const int in_off = Pp[0], in_mulp = Pp[1], ngrp = Pp[2];
-        const ln_f4* __restrict__ wf = reinterpret_cast<const ln_f4*>(g_W + Pp[3]) + lane;
+        const f32x4* __restrict__ wf = reinterpret_cast<const f32x4*>(g_W + Pp[3]) + lane;
         const float* __restrict__ xin[LN_TPW];
 #pragma unroll
         for (int t = 0; t < LN_TPW; ++t) xin[t] = A.x + row[t] * A.xs + in_off + acomp * in_mulp + 4 * g;
-        ln_f4 b[LN_TPW], bn[LN_TPW];
+        f32x4 b[LN_TPW], bn[LN_TPW];
         const bool k0 = 4 * g < in_mulp;
 #pragma unroll
-        for (int t = 0; t < LN_TPW; ++t) bn[t] = k0 ? *reinterpret_cast<const ln_f4*>(xin[t]) : (ln_f4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < LN_TPW; ++t) bn[t] = k0 ? *reinterpret_cast<const f32x4*>(xin[t]) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int G = 0; G < ngrp; ++G) {
 #pragma unroll
@@ -79,12 +76,12 @@ __global__ __launch_bounds__(256) void linear_planar_kernel(const LinArgs A, con
             if (G + 1 < ngrp) {                                // next K group in flight under this group's MFMAs
                 const bool kn = (16 * (G + 1) + 4 * g) < in_mulp;
 #pragma unroll
-                for (int t = 0; t < LN_TPW; ++t) bn[t] = kn ? *reinterpret_cast<const ln_f4*>(xin[t] + 16 * (G + 1)) : (ln_f4){0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < LN_TPW; ++t) bn[t] = kn ? *reinterpret_cast<const f32x4*>(xin[t] + 16 * (G + 1)) : (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt) {
                 if (rt < rtm) {
-                    const ln_f4 av = wf[(G * rtm + rt) * 64];
+                    const f32x4 av = wf[(G * rtm + rt) * 64];
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -101,10 +98,10 @@ __global__ __launch_bounds__(256) void linear_planar_kernel(const LinArgs A, con
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt) {
                 if (rt < rtm && 16 * rt + 4 * g < nstore) {
-                    ln_f4 v = acc[t][rt];
-                    if (A.res[0]) v += *reinterpret_cast<const ln_f4*>(A.res[0] + row[t] * A.rs[0] + col + 16 * rt);
-                    if (A.res[1]) v += *reinterpret_cast<const ln_f4*>(A.res[1] + row[t] * A.rs[1] + col + 16 * rt);
-                    *reinterpret_cast<ln_f4*>(yo + 16 * rt) = v;
+                    f32x4 v = acc[t][rt];
+                    if (A.res[0]) v += *reinterpret_cast<const f32x4*>(A.res[0] + row[t] * A.rs[0] + col + 16 * rt);
+                    if (A.res[1]) v += *reinterpret_cast<const f32x4*>(A.res[1] + row[t] * A.rs[1] + col + 16 * rt);
+                    *reinterpret_cast<f32x4*>(yo + 16 * rt) = v;
                 }
             }
         }

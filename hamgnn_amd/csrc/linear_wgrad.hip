@@ -10,17 +10,14 @@
 // chunk's rows four at a time (K = 4 rows per MFMA, one component at a time), the A operand (16 channels of x, 64 contiguous bytes per row)
 // is loaded once per K-step and feeds up to four MFMAs.  Every (unit, chunk) writes its partial [16 x 64] block to scratch; the host adds the
 // chunks in a fixed order (torch.sum over the chunk axis): deterministic, no float atomics.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
+#include "hg_device.h"
 
-typedef float lw_f4 __attribute__((ext_vector_type(4)));
 #define LW_ROWS 1024            // rows of a chunk (hamgnn_amd/ops.py:LW_ROWS)
 
 // unit record, int32[8]: {x_off, x_mulp, g_off, g_mulp, n = 2 l + 1, u0 (first input channel), v0 (first output channel), nv (output channels, <= 64)}
 __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restrict__ x, int64_t xs, const float* __restrict__ g, int64_t gs, int64_t rows,
                                                            const int* __restrict__ units, float* __restrict__ part, int nunits) {
-    __shared__ lw_f4 red[3][4][64];                            // waves 1..3 hand their accumulators to wave 0
+    __shared__ f32x4 red[3][4][64];                            // waves 1..3 hand their accumulators to wave 0
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = lane & 15, kk = lane >> 4;
     const int* __restrict__ U = units + blockIdx.x * 8;
@@ -32,9 +29,9 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
     bool va[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) va[t] = t < nt && v0 + 16 * t + i < g_mulp;
-    lw_f4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (lw_f4){0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const float* __restrict__ xb = x + x_off + u0 + i;
     const float* __restrict__ gb = g + g_off + v0 + i;
     // K-steps: (4 consecutive rows) x component; the four waves interleave the row groups

@@ -13,11 +13,7 @@
 //   Gate stage   : one wave per row, in place: the row's distinct activated scalars (scalars and gate channels) are overwritten by their
 //                  activation, every output is then a look-up (x the gate's value); all outputs of the row are held in registers before the
 //                  first is written.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-
-typedef float rp_f4 __attribute__((ext_vector_type(4)));
+#include "hg_device.h"
 
 #ifndef RP_NW
 #define RP_NW 16                // waves of the workgroup (plan.RP_NW): the stages are latency-bound chains, the LDS holds one workgroup per CU
@@ -46,6 +42,7 @@ struct RpArgs {
     float cst[5];
 };
 
+// (not row_ops.hip's hg_act: hardware exp / log / divide and threshold 15 here, log1pf / tanhf and threshold 20 there -- merging the two changes results)
 __device__ __forceinline__ float rp_act(float x, int id, const float* cst) {
     switch (id) {
         case 1: return cst[1] * ((x > 15.f ? x : __logf(1.f + __expf(x))) - 0.6931471805599453f);     // shifted softplus (hardware exp / log: abs. error ~1e-7)
@@ -56,20 +53,18 @@ __device__ __forceinline__ float rp_act(float x, int id, const float* cst) {
     }
 }
 
-__device__ __forceinline__ rp_f4 rp_mfma(float a, float b, rp_f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ void rp_load_w(rp_f4 (&w)[4], const float* __restrict__ W, int w_off, int nsteps, int lane) {
+__device__ __forceinline__ void rp_load_w(f32x4 (&w)[4], const float* __restrict__ W, int w_off, int nsteps, int lane) {
     const int ngrp = (nsteps + 3) >> 2;
     const float* __restrict__ wl = W + w_off + lane * 4;
 #pragma unroll
-    for (int G = 0; G < 4; ++G) w[G] = G < ngrp ? *reinterpret_cast<const rp_f4*>(wl + G * 256) : rp_f4{0.f, 0.f, 0.f, 0.f};
+    for (int G = 0; G < 4; ++G) w[G] = G < ngrp ? *reinterpret_cast<const f32x4*>(wl + G * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // one linear unit: all components of 16 output channels of one output block from one input block; w: the unit's weight fragments.
 // NG = groups of 4 K-steps (compile time: no branch between an operand read and its MFMA); the steps of the last group beyond the block's
 // channels multiply zero weights -- what they read is the next component / stale row content, finite because the buffers are zeroed once
 template <int NG>
-__device__ __forceinline__ void rp_unit_ng(const int* __restrict__ U, const rp_f4 (&w)[4], const float* __restrict__ src, float* __restrict__ dst,
+__device__ __forceinline__ void rp_unit_ng(const int* __restrict__ U, const f32x4 (&w)[4], const float* __restrict__ src, float* __restrict__ dst,
                                            int rs_src, int rs_dst, int lane) {
     const int in_off = U[0], in_mulp = U[1], out_off = U[3], out_mulp = U[4], ncomp = U[5], nv4 = U[6], acc_flag = U[8];
     const int n = lane & 15, g = lane >> 4;
@@ -81,7 +76,7 @@ __device__ __forceinline__ void rp_unit_ng(const int* __restrict__ U, const rp_f
         const bool two = m + 1 < ncomp;
         const float* __restrict__ ba = b0 + m * in_mulp;
         const float* __restrict__ bb = two ? ba + in_mulp : ba;
-        rp_f4 c0 = rp_f4{0.f, 0.f, 0.f, 0.f}, c1 = rp_f4{0.f, 0.f, 0.f, 0.f};
+        f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
         if (two) {
             float xa[4 * NG], xb[4 * NG];
 #pragma unroll
@@ -91,8 +86,8 @@ __device__ __forceinline__ void rp_unit_ng(const int* __restrict__ U, const rp_f
             }
 #pragma unroll
             for (int st = 0; st < 4 * NG; ++st) {
-                c0 = rp_mfma(w[st >> 2][st & 3], xa[st], c0);
-                c1 = rp_mfma(w[st >> 2][st & 3], xb[st], c1);
+                c0 = hg_mfma_f32_16x16x4(w[st >> 2][st & 3], xa[st], c0);
+                c1 = hg_mfma_f32_16x16x4(w[st >> 2][st & 3], xb[st], c1);
             }
         } else {                                               // a single component: its K-steps alternate between the two accumulators
             float xa[4 * NG];
@@ -100,31 +95,31 @@ __device__ __forceinline__ void rp_unit_ng(const int* __restrict__ U, const rp_f
             for (int st = 0; st < 4 * NG; ++st) xa[st] = ba[4 * st];
 #pragma unroll
             for (int st = 0; st < 4 * NG; st += 2) {
-                c0 = rp_mfma(w[st >> 2][st & 3], xa[st], c0);
-                c1 = rp_mfma(w[(st + 1) >> 2][(st + 1) & 3], xa[st + 1], c1);
+                c0 = hg_mfma_f32_16x16x4(w[st >> 2][st & 3], xa[st], c0);
+                c1 = hg_mfma_f32_16x16x4(w[(st + 1) >> 2][(st + 1) & 3], xa[st + 1], c1);
             }
             c0 += c1;
         }
         if (store) {
             float* __restrict__ da = d0 + m * out_mulp;
-            if (acc_flag) c0 += *reinterpret_cast<const rp_f4*>(da);
-            *reinterpret_cast<rp_f4*>(da) = c0;
+            if (acc_flag) c0 += *reinterpret_cast<const f32x4*>(da);
+            *reinterpret_cast<f32x4*>(da) = c0;
             if (two) {
                 float* __restrict__ db = da + out_mulp;
-                if (acc_flag) c1 += *reinterpret_cast<const rp_f4*>(db);
-                *reinterpret_cast<rp_f4*>(db) = c1;
+                if (acc_flag) c1 += *reinterpret_cast<const f32x4*>(db);
+                *reinterpret_cast<f32x4*>(db) = c1;
             }
         }
     }
 }
 
-__device__ __forceinline__ void rp_unit(const int* __restrict__ U, const rp_f4 (&w)[4], const float* __restrict__ src, float* __restrict__ dst,
+__device__ __forceinline__ void rp_unit(const int* __restrict__ U, const f32x4 (&w)[4], const float* __restrict__ src, float* __restrict__ dst,
                                         int rs_src, int rs_dst, int lane) {
     switch ((U[2] + 3) >> 2) {
         case 0: {                                              // an output block without a path: zeros
             const int n = lane & 15, g = lane >> 4;
             if (g < U[6] && !U[8])
-                for (int m = 0; m < U[5]; ++m) *reinterpret_cast<rp_f4*>(dst + n * rs_dst + U[3] + 4 * g + m * U[4]) = rp_f4{0.f, 0.f, 0.f, 0.f};
+                for (int m = 0; m < U[5]; ++m) *reinterpret_cast<f32x4*>(dst + n * rs_dst + U[3] + 4 * g + m * U[4]) = f32x4{0.f, 0.f, 0.f, 0.f};
             break;
         }
         case 1: rp_unit_ng<1>(U, w, src, dst, rs_src, rs_dst, lane); break;
@@ -146,7 +141,7 @@ extern "C" int hg_prof_rp_read(unsigned long long* out, int reset) {
 #endif
 #define RP_PRE (256 / RP_TPR)    // float4 pieces of an input row per thread (rows up to 1024 floats)
 
-__device__ __forceinline__ void rp_fetch_rows(const RpArgs& A, int64_t r0, rp_f4 (&pre)[RP_PRE], int tid) {
+__device__ __forceinline__ void rp_fetch_rows(const RpArgs& A, int64_t r0, f32x4 (&pre)[RP_PRE], int tid) {
     const int row = tid >> RP_TPR_SH, j = tid & (RP_TPR - 1);
     int64_t r = r0 + row;
     r = r < A.rows ? r : A.rows - 1;
@@ -155,7 +150,7 @@ __device__ __forceinline__ void rp_fetch_rows(const RpArgs& A, int64_t r0, rp_f4
     const int np = A.din >> 2;
 #pragma unroll
     for (int k = 0; k < RP_PRE; ++k)
-        if (j + RP_TPR * k < np) pre[k] = *reinterpret_cast<const rp_f4*>(xr + 4 * (j + RP_TPR * k));
+        if (j + RP_TPR * k < np) pre[k] = *reinterpret_cast<const f32x4*>(xr + 4 * (j + RP_TPR * k));
 }
 
 extern "C" __global__ void __launch_bounds__(RP_NT)
@@ -183,8 +178,8 @@ row_program_kernel(const RpArgs A, const int* __restrict__ g_stages, const int* 
     __syncthreads();
     const int2* __restrict__ t_act = A.lds_tabs ? s_act : g_act;
     const int2* __restrict__ t_out = A.lds_tabs ? s_out : g_out;
-    rp_f4 pre[RP_PRE];
-    rp_f4 wcur[4], wnext[4];
+    f32x4 pre[RP_PRE];
+    f32x4 wcur[4], wnext[4];
 #ifdef HG_PROF
     unsigned long long last_ = __builtin_readcyclecounter();
 #endif
@@ -200,7 +195,7 @@ row_program_kernel(const RpArgs A, const int* __restrict__ g_stages, const int* 
             const int np = A.din >> 2;
 #pragma unroll
             for (int k = 0; k < RP_PRE; ++k)
-                if (j + RP_TPR * k < np) *reinterpret_cast<rp_f4*>(d + 4 * (j + RP_TPR * k)) = pre[k];
+                if (j + RP_TPR * k < np) *reinterpret_cast<f32x4*>(d + 4 * (j + RP_TPR * k)) = pre[k];
         }
         __syncthreads();
         RP_T(0);
@@ -272,10 +267,10 @@ row_program_kernel(const RpArgs A, const int* __restrict__ g_stages, const int* 
                 float* __restrict__ yr = A.y + r * A.ys;
                 const int np = A.dout >> 2;
                 for (int p = j; p < np; p += RP_TPR) {
-                    rp_f4 v = *reinterpret_cast<const rp_f4*>(sp + 4 * p);
-                    if (A.res[0]) v += *reinterpret_cast<const rp_f4*>(A.res[0] + r * A.rs[0] + 4 * p);
-                    if (A.res[1]) v += *reinterpret_cast<const rp_f4*>(A.res[1] + r * A.rs[1] + 4 * p);
-                    *reinterpret_cast<rp_f4*>(yr + 4 * p) = v;
+                    f32x4 v = *reinterpret_cast<const f32x4*>(sp + 4 * p);
+                    if (A.res[0]) v += *reinterpret_cast<const f32x4*>(A.res[0] + r * A.rs[0] + 4 * p);
+                    if (A.res[1]) v += *reinterpret_cast<const f32x4*>(A.res[1] + r * A.rs[1] + 4 * p);
+                    *reinterpret_cast<f32x4*>(yr + 4 * p) = v;
                 }
             }
         }

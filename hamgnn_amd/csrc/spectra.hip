@@ -3,12 +3,7 @@
 //   hg_dos_broaden:      D[j, g] = sum_s A(E_j, eps_s) W[s, g], A a normalised Gaussian: a GEMM whose left operand is generated in registers
 //   hg_dos_tetra:        the same GEMM with the linear tetrahedron method's corner weights (DOS or number of states) as the left operand
 // No atomics, no claim-order reduction: all kernels are bit-reproducible from launch to launch.  Callers allocate everything.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-#include "hamgnn_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "hg_device.h"
 
 // ------------------------------------------------------------------------------------------------ Mulliken weights
 // One workgroup owns one state row s; wave w owns the groups g = w, w + 4, ...  The lanes of a wave stride over the orbitals of a group in the

@@ -1,11 +1,123 @@
-// sym_contraction_nu.hip -- one term of the MACE symmetric contraction of a CorrProductBlock, generic in the order nu in {1 ... 4}, and its adjoint
+// sym_contraction.hip -- the MACE symmetric contraction of a CorrProductBlock on the nodes (gfx950; reference: hamgnn/nn/interaction_blocks.py:234-260 ->
+// toolbox/mace/modules/symmetric_contraction.py).  The three routes of hamgnn_amd/nn.py:CorrProductBlock:
+//   hg_sym_contraction                 the nu <= 2 part of every block (correlation 1 ... 4): writes the rows
+//   hg_sym_contraction3                the nu = 3 term of correlation 3 and 4, ADDED onto those rows (backward: hamgnn_amd/corr3.py)
+//   hg_sym_contraction_nu / _backward  one term of any order nu = 1 ... 4 and its adjoint: the nu = 4 term of correlation 4; every term under HG_CORR_KERNEL=nu
+// Hand-written HIP for gfx950 (CDNA4).
+#include "hg_device.h"
+
+// ------------------------------------------------------------------------------------------------ nu <= 2
+// MACE symmetric contraction with correlation <= 2 on the nodes (hamgnn/nn/interaction_blocks.py:234-260 ->
+// toolbox/mace/modules/symmetric_contraction.py:212-230), sparse form of the reference's dense einsums:
+//   out[o, c] = sum_x ( sum_(e in row1(o)) U1 W1[z, kap, c]  +  sum_(e in row2(o)) U2 W2[z, kap, c] x[c, i] ) x[c, x]
+// One workgroup per node; the node's hidden features x[c][ell] sit in LDS; one thread per (output element o, channel c).
+// Node-level and off in the shipped configurations: written for correctness and coalesced weight reads, not tuned.
+__global__ __launch_bounds__(256) void sym_contraction_kernel(const float* __restrict__ h, int64_t hs, const int64_t* __restrict__ z, int C, int num_ell,
+                                                              const int* __restrict__ ell_off, int nout, const int* __restrict__ out_off,
+                                                              const int* __restrict__ ptr1, const int4* __restrict__ ent1,
+                                                              const int* __restrict__ ptr2, const int4* __restrict__ ent2,
+                                                              const float* __restrict__ W1, int K1, const float* __restrict__ W2, int K2,
+                                                              float* __restrict__ out, int64_t os) {
+    extern __shared__ float xs[];                              // [num_ell][C]
+    const int64_t b = blockIdx.x;
+    const float* __restrict__ hb = h + b * hs;
+    for (int i = threadIdx.x; i < num_ell * C; i += blockDim.x) {
+        const int ell = i / C, c = i - ell * C;
+        xs[i] = hb[ell_off[ell] + c];
+    }
+    __syncthreads();
+    const int64_t zb = z[b];
+    const float* __restrict__ w1 = W1 + zb * (int64_t)K1 * C;
+    const float* __restrict__ w2 = W2 + zb * (int64_t)K2 * C;
+    for (int idx = threadIdx.x; idx < nout * C; idx += blockDim.x) {
+        const int o = idx / C, c = idx - o * C;
+        float acc = 0.f;
+        for (int e = ptr1[o]; e < ptr1[o + 1]; ++e) {
+            const int4 t = ent1[e];                            // {x, kappa, -, value}
+            acc = fmaf(__int_as_float(t.w) * w1[t.y * C + c], xs[t.x * C + c], acc);
+        }
+        for (int e = ptr2[o]; e < ptr2[o + 1]; ++e) {
+            const int4 t = ent2[e];                            // {x, i, kappa, value}
+            acc = fmaf(__int_as_float(t.w) * w2[t.z * C + c] * xs[t.y * C + c], xs[t.x * C + c], acc);
+        }
+        out[b * os + out_off[o] + c] = acc;
+    }
+}
+
+extern "C" int hg_sym_contraction(const float* h, int64_t h_stride, const int64_t* z, int64_t N, int C, int num_ell, const int32_t* ell_off,
+                                  int nout, const int32_t* out_off, const int32_t* ptr1, const int32_t* ent1, const int32_t* ptr2,
+                                  const int32_t* ent2, const float* W1, int K1, const float* W2, int K2, float* out, int64_t out_stride,
+                                  void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (N <= 0) return 0;
+    const size_t lds = sizeof(float) * (size_t)num_ell * C;
+    if (lds > 64 * 1024) return hg_fail(-2, "hg_sym_contraction: hidden features too wide for the LDS-resident kernel");
+    sym_contraction_kernel<<<dim3((unsigned)N), 256, lds, (hipStream_t)stream>>>(h, h_stride, z, C, num_ell, ell_off, nout, out_off, ptr1,
+                                                                                 (const int4*)ent1, ptr2, (const int4*)ent2, W1, K1, W2, K2, out,
+                                                                                 out_stride);
+    return hg_check_launch("hg_sym_contraction");
+}
+
+// ------------------------------------------------------------------------------------------------ nu = 3
+// The nu = 3 term of the MACE symmetric contraction of a CorrProductBlock built with `correlation: 3`
+// (hamgnn/nn/interaction_blocks.py:234-260 -> toolbox/mace/modules/symmetric_contraction.py:148-230: the main einsum
+// "[w] x v i k, ekc, bci, be -> bc [w] x v" whose two open component indices the following nu = 2 / nu = 1 steps contract with x again;
+// U_matrix_real of toolbox/mace/tools/cg.py:16-131 for three factors).  ADDED onto the rows that hg_sym_contraction (above) wrote for
+// nu <= 2:
+//     out[n, o, c] += sum_{(x, i, j, kap, v) in ent3[o]} v W3[z_n, kap, c] h[n, x, c] h[n, i, c] h[n, j, c]
+// with U_3 given sparsely by plan.py:sym_contraction_tables (entries in the reference's path order, CSR rows per output element o).
+// Node-level and optional (correlation 3 is not the reference's default): one workgroup per node, the node's hidden components in LDS, a lane
+// owns one (output element, channel) and walks its entry list in order -- a fixed summation order, no atomics.  HBM traffic per node: its hidden
+// row once, its output row read + written once; the entry table (12-100 k entries x 20 B) and the element's weight block stay in L2.
+#define C3_ENT_I32 5             // {x, i, j, kappa (global over the targets), value (float bits)}
+
+__global__ __launch_bounds__(256) void sym_contraction3_kernel(const float* __restrict__ h, int64_t hs, const int64_t* __restrict__ z, int C, int num_ell,
+                                                               const int* __restrict__ ell_off, int nout, const int* __restrict__ out_off,
+                                                               const int* __restrict__ ptr3, const int* __restrict__ ent3,
+                                                               const float* __restrict__ W3, int K3, float* __restrict__ out, int64_t os) {
+    extern __shared__ float xs[];                              // [num_ell][C]
+    const int64_t b = blockIdx.x;
+    const float* __restrict__ hb = h + b * hs;
+    for (int i = threadIdx.x; i < num_ell * C; i += blockDim.x) {
+        const int ell = i / C, c = i - ell * C;
+        xs[i] = hb[ell_off[ell] + c];
+    }
+    __syncthreads();
+    const float* __restrict__ w3 = W3 + z[b] * (int64_t)K3 * C;
+    for (int idx = threadIdx.x; idx < nout * C; idx += blockDim.x) {
+        const int o = idx / C, c = idx - o * C;
+        float acc = 0.f;
+        for (int e = ptr3[o]; e < ptr3[o + 1]; ++e) {
+            const int* __restrict__ t = ent3 + (int64_t)e * C3_ENT_I32;
+            const float w = __int_as_float(t[4]) * w3[t[3] * C + c];
+            acc = fmaf(w * xs[t[0] * C + c] * xs[t[1] * C + c], xs[t[2] * C + c], acc);
+        }
+        out[b * os + out_off[o] + c] += acc;
+    }
+}
+
+extern "C" int hg_sym_contraction3(const float* h, int64_t h_stride, const int64_t* z, int64_t N, int C, int num_ell, const int32_t* ell_off,
+                                   int nout, const int32_t* out_off, const int32_t* ptr3, const int32_t* ent3, const float* W3, int K3,
+                                   float* out, int64_t out_stride, void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (N <= 0) return 0;
+    if (!h || !z || !ell_off || !out_off || !ptr3 || !ent3 || !W3 || !out) return hg_fail(-1, "hg_sym_contraction3: null pointer");
+    const size_t lds = (size_t)num_ell * C * sizeof(float);
+    if (lds > 64 * 1024) return hg_fail(-2, "hg_sym_contraction3: hidden features too wide for the LDS-resident kernel");
+    sym_contraction3_kernel<<<dim3((unsigned)N), 256, lds, (hipStream_t)stream>>>(h, h_stride, z, C, num_ell, ell_off, nout, out_off, ptr3, ent3, W3, K3,
+                                                                                  out, out_stride);
+    return hg_check_launch("hg_sym_contraction3");
+}
+
+// ------------------------------------------------------------------------------------------------ any order nu = 1 ... 4 and its adjoint
+// One term of the MACE symmetric contraction of a CorrProductBlock, generic in the order nu in {1 ... 4}, and its adjoint
 // (reference: hamgnn/nn/interaction_blocks.py:234-260 -> toolbox/mace/modules/symmetric_contraction.py:148-230, U_matrix_real of
 // toolbox/mace/tools/cg.py:16-131).  Forward, ADDED onto rows that already exist:
 //     out[n, o, c] += sum_{e in ent[o]} v_e W[z_n, kap_e, c] prod_{t < nu} x[n, i_{e,t}, c]
 // with U_nu given sparsely by plan.sym_contraction_tables (CSR rows per output element o; a row of `ent` is {i_0 .. i_{nu-1}, kappa, .., value bits}:
 // kappa in column nu, the value in the last of max(4, nu + 2) columns -- the layout ent1 / ent2 / ent3 / ent4 share).
 //
-// Forward: the shape of sym_contraction3_kernel (csrc/corr3.hip) -- one workgroup per node, the node's hidden components in LDS, CSR rows per output
+// Forward: the shape of sym_contraction3_kernel (above) -- one workgroup per node, the node's hidden components in LDS, CSR rows per output
 // element.  At nu = 4 the rows are long and uneven (55 ... 148 paths per target, 10^3 - 10^5 entries per row) and nout * C can be far below the 256
 // lanes, so a row is dealt to S lanes (S a power of two chosen from nout * C alone, entry e of the row to lane e mod S); the S partial sums meet in LDS
 // and ONE lane adds them in the order 0 ... S-1: a fixed summation order, no atomics.
@@ -14,11 +126,6 @@
 // g_W[g, kap, c] = sum over the nodes of group g IN INDEX ORDER and the entries of kappa (table transposed by kappa, rows {planar offset of o, planar
 // offsets of the nu components, value bits}): a lane owns one (group, kappa, channel), so every element of g_W is written once, without atomics.  A
 // group is an element's node list (or a run of it; the caller adds the runs in order) or, under charge doping, the node itself.
-// Hand-written HIP for gfx950 (CDNA4).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-
 #define SN_THREADS 256
 
 static inline int sn_width(int nu) { return nu + 2 < 4 ? 4 : nu + 2; }

@@ -16,11 +16,7 @@
 // Workgroup = 256 threads = 4 waves (one per SIMD); wave w owns edges [64*block + 16*w, +16).  All operands stream from
 // L1/L2: weights are pre-packed in fragment order (one coalesced 256-B load per MFMA A operand), B operands are dword
 // loads of the planar rotated feature rows (4 consecutive channels per 16-B segment).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "hg_device.h"
 
 struct TpArgs {
     const float* src[4];
@@ -42,51 +38,18 @@ struct TpArgs {
     int64_t rstride[2];
 };
 
-#define SEG_UNROTATE 1
 #ifndef HG_TP_WAVES
 #define HG_TP_WAVES 2            // min waves per SIMD the register allocator leaves room for (measured: 2 beats 1, 3, 4 - r1 A/B)
 #endif
 
-__device__ __forceinline__ const float* pick_src(const TpArgs& A, int i) {
-    return i == 0 ? A.src[0] : (i == 1 ? A.src[1] : (i == 2 ? A.src[2] : A.src[3]));
-}
-__device__ __forceinline__ int64_t pick_stride(const TpArgs& A, int i) {
-    return i == 0 ? A.sstride[0] : (i == 1 ? A.sstride[1] : (i == 2 ? A.sstride[2] : A.sstride[3]));
-}
-
-// phase profiler (HG_PROF builds only, tests/bench_tp.py --prof): per-wave shader-clock time between probes, summed over waves
 #ifdef HG_PROF
-__device__ unsigned long long hg_prof_acc[16];
-struct Prof { unsigned long long t[12]; unsigned long long last; };
-#define HG_PROF_ARG , Prof& prof
-#define HG_PROF_PASS , prof
-#define HG_T(k)                                                      \
-    do {                                                             \
-        const unsigned long long t_ = __builtin_readcyclecounter();  \
-        prof.t[k] += t_ - prof.last;                                 \
-        prof.last = t_;                                              \
-    } while (0)
-#else
-#define HG_PROF_ARG
-#define HG_PROF_PASS
-#define HG_T(k)
+__device__ unsigned long long hg_prof_acc[16];                 // the phase times of this kernel (hg_device.h: HG_T), read by hg_prof_read
 #endif
 
-#ifndef HG_DMA_AUX
-#define HG_DMA_AUX 2              // cache policy of the B-operand DMA: nt (streamed once per CU; keeps the shared A lines in L1; r1 A/B: -3 %)
-#endif
 // tiles and DMA rings are wave-private: the four waves of a workgroup never exchange data, so a wave-local LDS fence
 // (LDS ops of one wave retire in order) replaces workgroup barriers and the waves free-run (their DMA waits interleave).
 #define HG_WAVE_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define HG_STAGE_FLOATS 2816      // wave-private LDS-DMA ring for B operands: 11 KiB = 11 x 1-KiB (float4) or 44 x 256-B (dword) slots
-
-// LDS-DMA: per-lane global address -> LDS at (wave-uniform base + lane * size); no VGPR round trip, counted by vmcnt
-__device__ __forceinline__ void hg_dma16(const float* __restrict__ gsrc, float* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, HG_DMA_AUX);
-}
-__device__ __forceinline__ void hg_dma4(const float* __restrict__ gsrc, float* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
-}
 
 // B-operand span of one (item, source): NC * mulp contiguous floats per edge row -> linear LDS image (see item_body).
 // Sources of a two-source item share the ring when both spans fit (slot = source index), else they take turns at offset 0.
@@ -100,7 +63,7 @@ __device__ __forceinline__ int span_slot_floats(const Span& sp, int si) { return
 __device__ __forceinline__ void issue_span(const TpArgs& A, const Span& sp, int si, float* __restrict__ stage, int64_t erow, int g) {
     const int sidx = si ? sp.s1 : sp.s0;
     const int P = (2 * sp.mm + 1) * (sp.in_mulp >> 2), nj = (P + 3) >> 2;
-    const float* __restrict__ row = pick_src(A, sidx) + erow * pick_stride(A, sidx) + sp.in_off + (sp.li - sp.mm) * sp.in_mulp;
+    const float* __restrict__ row = hg_pick4(A.src, sidx) + erow * hg_pick4(A.sstride, sidx) + sp.in_off + (sp.li - sp.mm) * sp.in_mulp;
     float* __restrict__ dst = stage + span_slot_floats(sp, si);
 #pragma unroll 1
     for (int j = 0; j < nj; ++j) {
@@ -504,7 +467,7 @@ __global__ __launch_bounds__(256, HG_TP_WAVES) void tp_fused_kernel(const TpArgs
     float* tile = lds + wave * A.tile_floats_wave;
     float* stage = tile + (A.tile_floats_wave - HG_STAGE_FLOATS);          // B-operand DMA ring behind the segment tile
 #ifdef HG_PROF
-    Prof prof;
+    HgProf prof;
     for (int k = 0; k < 12; ++k) prof.t[k] = 0;
     prof.last = __builtin_readcyclecounter();
     const unsigned long long t_begin = prof.last;

@@ -14,22 +14,8 @@
 // Items, fragments and weights are exactly those of the segment-stationary program (same planner output, regrouped).
 #include "tp_stage.h"
 
-// phase profiler (HG_PROF builds only, tests/bench_tp.py): per-wave shader-clock time between probes, summed over waves
 #ifdef HG_PROF
-__device__ unsigned long long hg_prof_is_acc[16];
-struct ProfIs { unsigned long long t[12]; unsigned long long last; };
-#define IS_PROF_ARG , ProfIs& prof
-#define IS_PROF_PASS , prof
-#define IS_T(k)                                                      \
-    do {                                                             \
-        const unsigned long long t_ = __builtin_readcyclecounter();  \
-        prof.t[k] += t_ - prof.last;                                 \
-        prof.last = t_;                                              \
-    } while (0)
-#else
-#define IS_PROF_ARG
-#define IS_PROF_PASS
-#define IS_T(k)
+__device__ unsigned long long hg_prof_is_acc[16];              // the phase times of this kernel (hg_device.h: HG_T), read by hg_prof_is_read
 #endif
 // broadcast of lane q of every row of 16 lanes to that row: DPP row_newbcast (gfx90a+): lanes (g, *) <- lane (g, q).
 // x * (lane q of v's row of 16 lanes) in ONE VALU instruction: v_mul_f32 with the DPP control on its first source (the compiler keeps the
@@ -59,7 +45,7 @@ __device__ __forceinline__ float is_mul_bcast(float v, float x, int q) {
 // works on the 2 MM remaining columns only -- column slot c < MM is real column c, slot c >= MM is real column c + 1.
 template <int MM, int RTM, bool SPLIT, bool ODD>
 __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict__ Wb, const int* __restrict__ it,
-                                        float* __restrict__ lds, int64_t erow, int lane, const IsHidden& hbr, int hbr_cls IS_PROF_ARG) {
+                                        float* __restrict__ lds, int64_t erow, int lane, const IsHidden& hbr, int hbr_cls HG_PROF_ARG) {
     constexpr int NCR = 2 * MM + 1;                            // real columns (fragment layouts of cf, tile columns)
     constexpr int NC = ODD ? 2 * MM : NCR;                     // column slots this item computes
 #define IS_COL(c) ((ODD && (c) >= MM) ? (c) + 1 : (c))
@@ -75,7 +61,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
     const int* __restrict__ rtab = reinterpret_cast<const int*>(lds + A.rowtab_off) + it[23];
     float* __restrict__ tbase = lds + (SPLIT ? A.tile_shift : 0) + (el - MM * 16);
     const float* __restrict__ stage = lds + A.stage_off;
-    IS_T(0);                                                    // dispatch
+    HG_T(0);                                                    // dispatch
 
     const int nsrc = so1 >= 0 ? 2 : 1;
     const int ngrp = (ksteps + 3) >> 2;
@@ -160,7 +146,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
         }
     }
 
-    IS_T(1);                                                    // radial scale
+    HG_T(1);                                                    // radial scale
     // ---------------------------------------------------------------- GEMM1: mid = A1 fragments x staged block
     f32x4 mid[RTM][NC];
 #pragma unroll
@@ -251,7 +237,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
         }
     }
 
-    IS_T(2);                                                    // GEMM1
+    HG_T(2);                                                    // GEMM1
     if (typ == 0) {
         const f32x4* __restrict__ a2 = reinterpret_cast<const f32x4*>(Wb + it[14]) + lane;
         const f32x4* __restrict__ cf = reinterpret_cast<const f32x4*>(Wb + it[13]) + g;     // [rt][c][g] float4
@@ -383,7 +369,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
                 for (int c = 0; c < NC; ++c) t0[r][IS_COL(c) * 16] = told[r][c] + mid[rt][c][r];
         }
     }
-    IS_T(3);                                                    // scale-mul + GEMM2 + write-back
+    HG_T(3);                                                    // scale-mul + GEMM2 + write-back
 #undef IS_COL
 #undef IS_NK2_OK
 }
@@ -715,9 +701,9 @@ __device__ __forceinline__ void post_is(const IsArgs& A, const float* __restrict
 }
 
 #define IS_CASE(MMv, RTMv) \
-    case (MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, false>(A, g_W, it, lds, erow, lane, hbr, hbr_cls IS_PROF_PASS); break;
+    case (MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, false>(A, g_W, it, lds, erow, lane, hbr, hbr_cls HG_PROF_PASS); break;
 #define IS_CASE_ODD(MMv, RTMv) \
-    case (64 + MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, true>(A, g_W, it, lds, erow, lane, hbr, hbr_cls IS_PROF_PASS); break;
+    case (64 + MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, true>(A, g_W, it, lds, erow, lane, hbr, hbr_cls HG_PROF_PASS); break;
 
 // A launch runs `nparts` sub-schedules (blockIdx.y) of the same program: every part owns a disjoint set of output segments and the
 // phases / groups / items that feed them (plan.py:is_schedule(parts=...)).  One part = the whole program (large edge counts); several
@@ -764,7 +750,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
     float* __restrict__ stage = lds + A.stage_off;
     int* __restrict__ ctr = reinterpret_cast<int*>(lds + A.ctr_off);
 #ifdef HG_PROF
-    ProfIs prof;
+    HgProf prof;
     for (int k = 0; k < 12; ++k) prof.t[k] = 0;
     prof.last = __builtin_readcyclecounter();
     const unsigned long long t_begin = prof.last;
@@ -776,7 +762,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
         const int* __restrict__ rt_g = g_rowtab + A.rowtab_begin;
         for (int i = threadIdx.x; i < A.rowtab_len; i += NT) rt_l[i] = rt_g[i];
     }
-    IS_T(4);                                                   // zero fill
+    HG_T(4);                                                   // zero fill
 
     for (int ph = ph0; ph < ph1; ++ph) {
         const int* __restrict__ P = g_phases + ph * 8;
@@ -791,7 +777,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
             for (int G = 0; G < 4; ++G) hv[G] = hbr_cls >= 0 ? *reinterpret_cast<const f32x4*>(hrow + 16 * G) : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         __syncthreads();                                       // every wave is done with the previous blocks (and the zero fill)
-        IS_T(5);                                               // waiting for the slowest wave of the previous phase
+        HG_T(5);                                               // waiting for the slowest wave of the previous phase
         if (threadIdx.x == 0) *ctr = g0;
 #pragma unroll 1
         for (int b = b0; b < b1; ++b) {
@@ -807,7 +793,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
                 default: break;
             }
 #ifdef HG_PROF                     // staging by kind: 8 = plain rows (LDS-DMA issue), 9 = gathered l = 0 rows, 10 = rotated l = 1..3, 11 = rotated l >= 4
-            if (!((A.rot_mask >> B[0]) & 1)) { IS_T(8); } else if (B[4] == 0) { IS_T(9); } else if (B[4] <= 3) { IS_T(10); } else { IS_T(11); }
+            if (!((A.rot_mask >> B[0]) & 1)) { HG_T(8); } else if (B[4] == 0) { HG_T(9); } else if (B[4] <= 3) { HG_T(10); } else { HG_T(11); }
 #endif
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -849,7 +835,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
         }
         __builtin_amdgcn_sched_barrier(0);                     // (the split stays on this side of the barrier: in the wait for the other waves' staging)
         __syncthreads();
-        IS_T(6);                                               // staging the phase's input blocks
+        HG_T(6);                                               // staging the phase's input blocks
         // work groups = all items of one (phase, output segment), claimed largest-first: dynamic balance, and a tile is only ever
         // updated by one wave between two barriers (the order of the adds into a tile cell is the program's: phases, then a group's items).
         // Parts with private tile copies (split launches of small crystals): every item is its own group and the groups are DEALT, not claimed
@@ -871,7 +857,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
             for (int ii = ib; ii < ie; ++ii) {
                 const int* __restrict__ it = g_items + ii * 24;
                 if (LITE) {                                    // lite_mode programs: their own (small) items, their own kernel instantiation
-                    IS_T(0);                                   // dispatch / claim
+                    HG_T(0);                                   // dispatch / claim
                     if (it[0] == 3) {                          // post-op of one segment (the part's last phase)
                         if (it[22] == 1) post_is<1>(A, g_W, it, lds, erow, lane);
                         else if (it[22] == 2) post_is<2>(A, g_W, it, lds, erow, lane);
@@ -883,7 +869,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
                     else if (it[9] == 2) item_lite<2>(A, g_W, it, lds, lane);
                     else if (it[9] == 3) item_lite<3>(A, g_W, it, lds, lane);
                     else item_lite<4>(A, g_W, it, lds, lane);
-                    if (it[0] == 3) { IS_T(3); } else { IS_T(2); }       // (profile slots: 2 = lite items / runs, 3 = post-ops)
+                    if (it[0] == 3) { HG_T(3); } else { HG_T(2); }       // (profile slots: 2 = lite items / runs, 3 = post-ops)
                     continue;
                 }
                 switch (it[6] * 8 + it[9] + ((it[0] == 0 && it[7]) ? 64 : 0)) {
@@ -934,13 +920,13 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
                     if (!(T8[7] & SEG_UNROTATE) || l2 == lprev) continue;      // one block per l (segments are ordered by batch, l)
                     lprev = l2;
                     const int nn = (2 * l2 + 1) * (2 * l2 + 1);
-                    const float* __restrict__ D = A.wig + erow * A.nW + is_pick_wig_off(A, l2);
+                    const float* __restrict__ D = A.wig + erow * A.nW + hg_pick8(A.wig_off, l2);
                     const int nj = (nn + 3) >> 2;
 #pragma unroll 1
                     for (int j = wave; j < nj; j += NW) {      // image [m * NCO + a][edge]
                         int idx = 4 * j + g;
                         idx = idx < nn ? idx : nn - 1;
-                        is_dma4(D + idx, stage + T8[6] + j * 64);
+                        hg_dma4(D + idx, stage + T8[6] + j * 64);
                     }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -960,7 +946,7 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
             default: break;
         }
     }
-    IS_T(7);                                                   // epilogue
+    HG_T(7);                                                   // epilogue
 #ifdef HG_PROF
     if (lane == 0) {
         for (int k = 0; k < 12; ++k) atomicAdd(&hg_prof_is_acc[k], prof.t[k]);

@@ -2,12 +2,8 @@
 // of the input-stationary edge kernel csrc/tp_is.hip (dynamic work claiming, register-chained row-tile chunks).
 // Hand-written HIP for gfx950 (CDNA4).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
+#include "hg_device.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // the 16 edges' hidden rows of a phase's radial MLP as B operands of v_mfma_f32_16x16x32_f16: x = hi + lo (csrc/tp_is.hip, plan/program.py:w3_split_fill)
 // c0 = 2^-(sw + sh): undoes the weights' exponent and the tile's
 struct IsHidden { f16x8 hi[2], lo[2]; float c0; };
@@ -88,30 +84,6 @@ __device__ __forceinline__ float is_seg_scan(float x, const IsScan& sc) {
     x = fmaf(sc.m[2], is_dpp_f<0x114>(x), x);
     x = fmaf(sc.m[3], is_dpp_f<0x118>(x), x);
     return x;
-}
-
-#define SEG_UNROTATE 1
-#define SEG_ATOMIC 2             // (split launches only) the segment is one of TWO copies that share an output block: each adds its half of the items' sum
-                                 // (plan.split_heavy_segments: the heaviest output irreps of a small crystal's launch on two workgroups; the rows are zero-filled by the host)
-
-__device__ __forceinline__ const float* is_pick_src(const IsArgs& A, int i) {
-    return i == 0 ? A.src[0] : (i == 1 ? A.src[1] : (i == 2 ? A.src[2] : A.src[3]));
-}
-__device__ __forceinline__ int64_t is_pick_stride(const IsArgs& A, int i) {
-    return i == 0 ? A.sstride[0] : (i == 1 ? A.sstride[1] : (i == 2 ? A.sstride[2] : A.sstride[3]));
-}
-// (kernel-argument arrays are only ever indexed through select chains: a dynamically indexed member makes the compiler copy the whole
-//  argument block into per-lane scratch -- 232 B x 2.1 M lanes = 0.5 GB of HBM writes per launch in the first build)
-__device__ __forceinline__ int is_pick_wig_off(const IsArgs& A, int l) {
-    return l == 0 ? A.wig_off[0] : (l == 1 ? A.wig_off[1] : (l == 2 ? A.wig_off[2] : (l == 3 ? A.wig_off[3] : (l == 4 ? A.wig_off[4] :
-           (l == 5 ? A.wig_off[5] : (l == 6 ? A.wig_off[6] : A.wig_off[7]))))));
-}
-// LDS-DMA: per-lane global address -> LDS at (wave-uniform base + lane * size); counted by vmcnt
-__device__ __forceinline__ void is_dma16(const float* __restrict__ gsrc, float* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
-}
-__device__ __forceinline__ void is_dma4(const float* __restrict__ gsrc, float* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
 }
 
 // the four channels of a lane go out as one 16-byte store -- or, AT (split launches) and the segment flagged SEG_ATOMIC, as four hardware float adds
@@ -220,11 +192,11 @@ __device__ __forceinline__ void stage_block(const IsArgs& A, const int* __restri
         // sender and receiver rows of the node branch share the edge's Wigner row: one output piece t = a * P1 + p (component a,
         // channels 4p..4p+3) of BOTH sources per (wave, g) slot and step -- 2 N float4 loads of the node rows + the N entries of
         // row a in flight together, 2 N float4 FMAs, two ds_write_b128 straight into the operand images
-        const int64_t* __restrict__ ix0 = s0 == 0 ? A.idx[0] : (s0 == 1 ? A.idx[1] : (s0 == 2 ? A.idx[2] : A.idx[3]));
-        const int64_t* __restrict__ ix1 = s1 == 0 ? A.idx[0] : (s1 == 1 ? A.idx[1] : (s1 == 2 ? A.idx[2] : A.idx[3]));
+        const int64_t* __restrict__ ix0 = hg_pick4(A.idx, s0);
+        const int64_t* __restrict__ ix1 = hg_pick4(A.idx, s1);
         const int64_t r0 = ix0 ? ix0[erow] : erow, r1 = ix1 ? ix1[erow] : erow;
-        const float* __restrict__ row0 = is_pick_src(A, s0) + r0 * is_pick_stride(A, s0) + in_off;
-        const float* __restrict__ row1 = is_pick_src(A, s1) + r1 * is_pick_stride(A, s1) + in_off;
+        const float* __restrict__ row0 = hg_pick4(A.src, s0) + r0 * hg_pick4(A.sstride, s0) + in_off;
+        const float* __restrict__ row1 = hg_pick4(A.src, s1) + r1 * hg_pick4(A.sstride, s1) + in_off;
         const float* __restrict__ D = A.wig + erow * A.nW + A.wig_off[L];
         float* __restrict__ d0 = stage + P[6] + el * 4;
         float* __restrict__ d1 = stage + P[7] + el * 4;
@@ -267,9 +239,9 @@ __device__ __forceinline__ void stage_block(const IsArgs& A, const int* __restri
     }
     for (int si = 0; si < nsrc; ++si) {
         const int sidx = si ? s1 : s0;
-        const int64_t* __restrict__ ix = sidx == 0 ? A.idx[0] : (sidx == 1 ? A.idx[1] : (sidx == 2 ? A.idx[2] : A.idx[3]));
+        const int64_t* __restrict__ ix = hg_pick4(A.idx, sidx);
         const int64_t r = ix ? ix[erow] : erow;
-        const float* __restrict__ row = is_pick_src(A, sidx) + r * is_pick_stride(A, sidx) + in_off;
+        const float* __restrict__ row = hg_pick4(A.src, sidx) + r * hg_pick4(A.sstride, sidx) + in_off;
         float* __restrict__ dst = stage + (si ? P[7] : P[6]);
         if (si ? rot1 : rot0) {
             const float* __restrict__ D = A.wig + erow * A.nW + A.wig_off[L];
@@ -293,7 +265,7 @@ __device__ __forceinline__ void stage_block(const IsArgs& A, const int* __restri
             for (int j = wave; j < nj; j += NW) {              // the waves share the block's DMA instructions
                 int p = 4 * j + g;
                 p = p < Pfull ? p : Pfull - 1;
-                is_dma16(row + 4 * p, dst + j * 256);
+                hg_dma16(row + 4 * p, dst + j * 256);
             }
         }
     }

@@ -1,5 +1,5 @@
 // tp_wgrad.hip -- fused WEIGHT gradients of the weighted tensor-product branches of a MessagePackBlock (the backward of
-// /root/reference/hamgnn/nn/message_passing.py:191-231 with respect to tensor_product.weight, linear_scaler.linear_out.weight,
+// hamgnn/nn/message_passing.py:191-231 with respect to tensor_product.weight, linear_scaler.linear_out.weight,
 // linear_out.weight and -- through gs -- the radial weight generators).  Hand-written HIP for gfx950 (CDNA4), fp32 MFMA.
 //
 // Weight-stationary where the forward (csrc/tp_is.hip) is input-stationary: a workgroup owns one UNIT of plan.WgFused = up to four
@@ -19,11 +19,7 @@
 // 16 channels) are both conflict-free.
 // Partial sums of the splits (blockIdx.y) and of the edge-tile copies inside a workgroup go to separate accumulator blocks; the host adds
 // them in a fixed order (bit-reproducible, no float atomics).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "hg_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "hg_device.h"
 
 #define WG_UNIT_I32 64
 #define WG_NT 256
@@ -47,15 +43,6 @@ struct WgArgs {
     int hidden;
 };
 
-__device__ __forceinline__ const float* wg_pick_src(const WgArgs& A, int i) {
-    return i == 0 ? A.src[0] : (i == 1 ? A.src[1] : (i == 2 ? A.src[2] : A.src[3]));
-}
-__device__ __forceinline__ int64_t wg_pick_stride(const WgArgs& A, int i) {
-    return i == 0 ? A.sstride[0] : (i == 1 ? A.sstride[1] : (i == 2 ? A.sstride[2] : A.sstride[3]));
-}
-
-__device__ __forceinline__ f32x4 wg_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // issue the loads of one iteration's operand rows (ET x 16 edges x [x0 | x1 | g spans | h]) into registers.  16 / ET threads share a row
 // (piece pos = j + (16 / ET) n of row tid / (16 / ET)): no division, one set of row pointers per thread and iteration
 template <int NP>
@@ -65,8 +52,8 @@ __device__ __forceinline__ void wg_load(const WgArgs& A, const int* __restrict__
     const int row = tid >> sh, j = tid & (tpr - 1);
     int64_t e = e0 + row;
     e = e < A.rows ? e : A.rows - 1;                           // tail rows read a valid row; their products are zeroed (see wg_wave)
-    const float* __restrict__ r0 = wg_pick_src(A, U[1]) + U[3] + e * wg_pick_stride(A, U[1]);
-    const float* __restrict__ r1 = wg_pick_src(A, U[2]) + U[3] + e * wg_pick_stride(A, U[2]);
+    const float* __restrict__ r0 = hg_pick4(A.src, U[1]) + U[3] + e * hg_pick4(A.sstride, U[1]);
+    const float* __restrict__ r1 = hg_pick4(A.src, U[2]) + U[3] + e * hg_pick4(A.sstride, U[2]);
     const float* __restrict__ rg = A.g + e * A.gstride;
     const float* __restrict__ rh = (U[7] ? A.h[1] : A.h[0]) + e * A.hstride;
     const int p1 = XP, p2 = nsrc == 2 ? 2 * XP : XP;           // [0, p1) source 0, [p1, p2) source 1
@@ -226,8 +213,8 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                             for (int c = 0; c < NC; ++c) {
                                 const int cl = par ? (NC - 1 - c) : c;
                                 const float a = xs[cl * in_mulp + 4 * step];
-                                if (NC == 1 && (q & 1)) mid2 = wg_mfma(a, fW[s][G][q], mid2);
-                                else mid[c] = wg_mfma(a, fW[s][G][q], mid[c]);
+                                if (NC == 1 && (q & 1)) mid2 = hg_mfma_f32_16x16x4(a, fW[s][G][q], mid2);
+                                else mid[c] = hg_mfma_f32_16x16x4(a, fW[s][G][q], mid[c]);
                             }
                             WG_SGB(NC > 1, NC)
                         }
@@ -246,8 +233,8 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
 #pragma unroll
                             for (int c = 0; c < NC; ++c) {
                                 const float a = ga[c * g_mulp + 4 * step];
-                                if (NC == 1 && (q & 1)) bm2 = wg_mfma(a, fL[G][q], bm2);
-                                else bm[c] = wg_mfma(a, fL[G][q], bm[c]);
+                                if (NC == 1 && (q & 1)) bm2 = hg_mfma_f32_16x16x4(a, fL[G][q], bm2);
+                                else bm[c] = hg_mfma_f32_16x16x4(a, fL[G][q], bm[c]);
                             }
                             WG_SGB(NC > 1, NC)
                         }
@@ -262,8 +249,8 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                 for (int G = 0; G < G3; ++G) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        if (q & 1) sv2 = wg_mfma(ha[4 * (4 * G + q)], f3[G][q], sv2);
-                        else sv = wg_mfma(ha[4 * (4 * G + q)], f3[G][q], sv);
+                        if (q & 1) sv2 = hg_mfma_f32_16x16x4(ha[4 * (4 * G + q)], f3[G][q], sv2);
+                        else sv = hg_mfma_f32_16x16x4(ha[4 * (4 * G + q)], f3[G][q], sv);
                     }
                     WG_SGB(true, 4)
                 }
@@ -308,11 +295,11 @@ __device__ __forceinline__ void wg_wave(const WgArgs& A, const int* __restrict__
                     for (int s = 0; s < NSRC; ++s) {
                         const float* __restrict__ xs = xb + (s ? xoff1 : 0) + xc0 + cl * in_mulp + r * RS;
 #pragma unroll
-                        for (int t = 0; t < G1; ++t) accW[s][t] = wg_mfma(xs[16 * t], bm[c][r], accW[s][t]);
+                        for (int t = 0; t < G1; ++t) accW[s][t] = hg_mfma_f32_16x16x4(xs[16 * t], bm[c][r], accW[s][t]);
                     }
                     const float* __restrict__ gb = xb + goff + c * g_mulp + r * RS;
 #pragma unroll
-                    for (int t = 0; t < G2; ++t) accL[t] = wg_mfma(gb[16 * t], mid[c][r], accL[t]);
+                    for (int t = 0; t < G2; ++t) accL[t] = hg_mfma_f32_16x16x4(gb[16 * t], mid[c][r], accL[t]);
                     WG_SGB(true, NSRC * G1 + G2)
                 }
             }

@@ -3,7 +3,7 @@ hamgnn/models/base_model.py:237-288; used in hamgnn/models/hamgnn_conv.py:252-28
 radius_scale * (r_i + r_j) (the radii table of basis.atomic_radii, 10.0 for an element the table lacks: base_model.py:63, 84); the layers run
 on that graph and the representation goes back on the edges the data came with, through `matching_edges`.
 
-The reference rebuilds the graph on the host (ASE) in every forward.  Here it is built on the device -- csrc/aux_kernels.hip: hg_neighbour_bin
+The reference rebuilds the graph on the host (ASE) in every forward.  Here it is built on the device -- csrc/neighbour.hip: hg_neighbour_bin
 (cell list in fractional coordinates), hg_neighbour_pairs (count pass, prefix sum, fill pass: one packed int64 key per edge), a sort of the keys
 (their ascending order IS the canonical edge order (i, j, S0, S1, S2), so nothing depends on scheduling), hg_neighbour_decode -- and kept on the
 data object until `pos`, `cell`, `z`, `batch`, `edge_index` or `cell_shift` are replaced or changed in place (the mechanism of topo.py).  A build
@@ -26,7 +26,7 @@ DEFAULT_RADIUS = 10.0                                          # base_model.py:6
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe "
            "Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt Au Hg Tl Pb Bi Po At Rn Fr Ra Ac Th Pa U Np Pu Am Cm Bk Cf Es Fm Md No Lr "
            "Rf Db Sg Bh Hs Mt Ds Rg Cn Nh Fl Mc Lv Ts Og").split()
-KEY_ATOM_BITS, KEY_SHIFT_OFF, KEY_SHIFT_MAX = 24, 16, 15       # the packed edge key of csrc/aux_kernels.hip: i << 39 | j << 15 | three 5-bit shifts
+KEY_ATOM_BITS, KEY_SHIFT_OFF, KEY_SHIFT_MAX = 24, 16, 15       # the packed edge key of csrc/neighbour.hip: i << 39 | j << 15 | three 5-bit shifts
 _FLAG_TEXT = {1: "a singular or non-finite cell (or no positive radius)", 2: "more than 15 periodic images along a lattice direction: the radii are far larger than the cell",
               4: "a neighbour table was too small (inputs changed while the graph was built?)", 8: "a non-finite position or a batch index outside the cells given"}
 _TABLES = {}

@@ -1355,7 +1355,7 @@ class CorrProductBlock(nn.Module):
     """Drop-in for hamgnn/nn/interaction_blocks.py:168-260 (correlation 1, 2 -- the reference default --, 3 or 4): linear_pre -> symmetric
     contraction with element-dependent weights -> prod.linear -> linear_out (+ linear_sc skip), all on planar node rows; same parameter
     names.  The nu <= 2 part of the contraction is the hg_sym_contraction kernel, the nu = 3 term hg_sym_contraction3 (backward: hamgnn_amd/corr3.py),
-    the nu = 4 term and its adjoint the order-generic kernels of csrc/sym_contraction_nu.hip.  HG_CORR_KERNEL=nu in the environment sends EVERY
+    the nu = 4 term and its adjoint the order-generic kernels of csrc/sym_contraction.hip.  HG_CORR_KERNEL=nu in the environment sends EVERY
     term, forward and adjoint, through the generic kernels (opt-in; unset, correlation <= 3 launches what it always launched)."""
 
     def __init__(self, irreps_node_feats, num_hidden_features, correlation, num_elements, use_skip_connections=True):

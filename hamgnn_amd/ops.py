@@ -90,7 +90,7 @@ def check_build_config():
 
 
 def w3_split_refill(w: torch.Tensor, se, so, dh, dl, scale: float, lo_scale: float) -> torch.Tensor:
-    """the split-half-precision twins of the fp32 W3 blocks of the packed weight blob `w`, rewritten IN PLACE by one launch (csrc/aux_kernels.hip:hg_w3_split_refill; index
+    """the split-half-precision twins of the fp32 W3 blocks of the packed weight blob `w`, rewritten IN PLACE by one launch (csrc/radial.hip:hg_w3_split_refill; index
     tensors: DeviceProgram.refresh_w3_split); returns the device scalar max |w 2^s| for the lazy range check (check_w3_split)"""
     _require_gpu(w)
     assert w.dtype == torch.float32 and w.is_contiguous() and all(t.dtype == torch.int64 and t.is_contiguous() for t in (se, so, dh, dl))
@@ -1002,7 +1002,7 @@ def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
 
 @_on_tensor_device
 def sym_contraction3(h, z, C, tab, W3, out):
-    """adds the nu = 3 term of a `correlation: 3` block to the rows `out` that sym_contraction returned (in place; csrc/corr3.hip)"""
+    """adds the nu = 3 term of a `correlation: 3` block to the rows `out` that sym_contraction returned (in place; csrc/sym_contraction.hip)"""
     _require_gpu(h)
     check(lib().hg_sym_contraction3(ptr(h), i64(h.stride(0)), ptr(z), i64(h.shape[0]), i32(C), i32(tab["num_ell"]), ptr(tab["ell_off"]), i32(tab["nout"]),
                                     ptr(tab["out_off"]), ptr(tab["ptr3"]), ptr(tab["ent3"]), ptr(W3), i32(W3.shape[1]), ptr(out), i64(out.stride(0)),
@@ -1012,7 +1012,7 @@ def sym_contraction3(h, z, C, tab, W3, out):
 
 @_on_tensor_device
 def sym_contraction_nu(nu, h, z, C, tab, W, out):
-    """adds the term of order nu (1 ... 4) of the symmetric contraction to the rows `out` (in place; csrc/sym_contraction_nu.hip): the nu = 4 term of a
+    """adds the term of order nu (1 ... 4) of the symmetric contraction to the rows `out` (in place; csrc/sym_contraction.hip): the nu = 4 term of a
     `correlation: 4` block onto what sym_contraction / sym_contraction3 wrote, or every term onto zeros (HG_CORR_KERNEL=nu)"""
     _require_gpu(h)
     h = h.contiguous()

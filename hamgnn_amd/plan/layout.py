@@ -97,6 +97,6 @@ def tp_instructions(irreps1: Irreps, irreps2: Irreps, target: Irreps):
 # ------------------------------------------------------------------------------------------------ small device tables
 
 # e3nn normalize2mom constants (E_{z~N(0,1)}[act(z)^2]^(-1/2), e3nn's 1e6-sample Monte-Carlo recipe with CPU seed 0; values
-# reproduced with torch 2.10).  Index = activation id of csrc/aux_kernels.hip:hg_act.
+# reproduced with torch 2.10).  Index = activation id of csrc/row_ops.hip:hg_act.
 ACT_NONE, ACT_SSP, ACT_TANH, ACT_SILU, ACT_ABS = 0, 1, 2, 3, 4
 ACT_CONSTS = np.array([1.0, 1.878204668541552, 1.5937334472592692, 1.6791767923989418, 1.0], dtype=np.float32)

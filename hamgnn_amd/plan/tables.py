@@ -175,7 +175,7 @@ def gate_tables(feature_irreps):
 
 
 def norm_act_table(irreps) -> np.ndarray:
-    """int32[nchan][2] = {offset of the irrep copy's first component in the planar row, component stride | components << 16} of csrc/aux_kernels.hip:
+    """int32[nchan][2] = {offset of the irrep copy's first component in the planar row, component stride | components << 16} of csrc/row_ops.hip:
     norm_act_kernel (e3nn NormActivation: one norm per irrep COPY)"""
     lay = PlanarLayout(irreps)
     out = []
@@ -645,7 +645,7 @@ def sym_contraction_tables(irreps_hidden: Irreps, correlation: int = 2):
       ell_off[i]  planar offset of ell component i (channel 0) in the hidden layout,   out_off[o] same for output element o = (k, w)
       ent1 rows (x, kappa_global, value-bits), ent2 rows (x, i, kappa_global, value-bits), ent3 rows (x, i, j, kappa_global, value-bits);
       kappa_global indexes the concatenated weights of all targets.  ent1 / ent2 feed hg_sym_contraction, ent3 hamgnn_amd/corr3.py.
-    correlation 4 adds ptr4, ent4 rows (x, i, j, l, kappa_global, value-bits) and K4 (_sym4_tables; csrc/sym_contraction_nu.hip); everything
+    correlation 4 adds ptr4, ent4 rows (x, i, j, l, kappa_global, value-bits) and K4 (_sym4_tables; csrc/sym_contraction.hip); everything
     listed above is then what correlation 3 returns."""
     assert correlation in (1, 2, 3, 4), "correlation > 4 is not built"
     lay = PlanarLayout(irreps_hidden)
@@ -786,7 +786,7 @@ def _sym4_tables(irs, sl):
 
 
 def sym_contraction_adjoint_tables(tab, nu: int):
-    """The nu-th entry list of sym_contraction_tables transposed twice for hg_sym_contraction_nu_backward (csrc/sym_contraction_nu.hip):
+    """The nu-th entry list of sym_contraction_tables transposed twice for hg_sym_contraction_nu_backward (csrc/sym_contraction.hip):
       ptrH int32[num_ell + 1], entH int32[., nu + 2]  by component: for every (entry, position t) whose position reads the component, in (entry, t)
                                                       order, {output element o, the other nu - 1 components, kappa, value-bits}
       ptrW int32[K + 1],       entW int32[., nu + 2]  by kappa, entries in order: {planar offset of o, planar offsets of the nu components, value-bits}

@@ -325,14 +325,14 @@ int hg_sym_contraction(const float* h, int64_t h_stride, const int64_t* z, int64
                        void* stream);
 
 /* The nu = 3 term of the same contraction for a block built with `correlation: 3` (symmetric_contraction.py:148-230: the main einsum over
- * U_matrix_real(.., correlation = 3), cg.py:16-131), ADDED onto the rows hg_sym_contraction wrote (csrc/corr3.hip):
+ * U_matrix_real(.., correlation = 3), cg.py:16-131), ADDED onto the rows hg_sym_contraction wrote (csrc/sym_contraction.hip):
  *   out[o, c] += sum_{(x, i, j, kap, v) in ent3[o]} v W3[z, kap, c] h[c, x] h[c, i] h[c, j]
  * ptr3 int32[nout + 1], ent3 int32[.][5] = {x, i, j, kappa, value bits} (plan.py:sym_contraction_tables), W3 [num_elements][K3][C].           */
 int hg_sym_contraction3(const float* h, int64_t h_stride, const int64_t* z, int64_t N, int C, int num_ell, const int32_t* ell_off,
                         int nout, const int32_t* out_off, const int32_t* ptr3, const int32_t* ent3, const float* W3, int K3,
                         float* out, int64_t out_stride, void* stream);
 
-/* One term of the same contraction, generic in the order nu = 1 ... 4 (csrc/sym_contraction_nu.hip), ADDED onto rows that exist:
+/* One term of the same contraction, generic in the order nu = 1 ... 4 (csrc/sym_contraction.hip), ADDED onto rows that exist:
  *   out[o, c] += sum_{e in ent[o]} v_e W[z, kap_e, c] prod_{t < nu} h[c, i_{e,t}]
  * ptr int32[nout + 1] / ent = the nu-th entry list of plan.sym_contraction_tables: rows of max(4, nu + 2) int32 {i_0 .. i_{nu-1}, kappa, .., value bits}
  * (kappa in column nu, the value in the last column), W [num_elements][K][C].  A `correlation: 4` block adds its nu = 4 term with it; with

@@ -1,7 +1,7 @@
-"""Micro-benchmark of the order-generic symmetric-contraction kernels (csrc/sym_contraction_nu.hip), one JSON line per measurement:
+"""Micro-benchmark of the order-generic symmetric-contraction kernels (csrc/sym_contraction.hip), one JSON line per measurement:
   (a) nu = 4: time per launch of hg_sym_contraction_nu and of hg_sym_contraction_nu_backward (element weights and per-node weights) on `--nodes` nodes
       of `--irreps` with `--hidden` channels, the planner's default (reference) path list;
-  (b) nu = 3, what HG_CORR_KERNEL=nu exchanges: the generic forward against hg_sym_contraction3 (csrc/corr3.hip), the generic adjoint against the torch
+  (b) nu = 3, what HG_CORR_KERNEL=nu exchanges: the generic forward against hg_sym_contraction3 (csrc/sym_contraction.hip), the generic adjoint against the torch
       backward of hamgnn_amd/corr3.py, same tables, same inputs; the largest difference between the two routes is printed with the times.
 Warm-up launches first, then `reps` repetitions of the same call between two events.  HG_LIB_PATH selects the .so."""
 import argparse, json, os, sys, time

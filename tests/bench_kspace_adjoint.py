@@ -1,4 +1,4 @@
-"""Micro-benchmark of the k-space adjoint (csrc/head.hip: hg_hk_assemble_adjoint) inside kspace.band_energy_backward: one synthetic crystal (default 64 atoms,
+"""Micro-benchmark of the k-space adjoint (csrc/kspace.hip: hg_hk_assemble_adjoint) inside kspace.band_energy_backward: one synthetic crystal (default 64 atoms,
 nao 19, 16 k-points), once with the kernel and once with HG_HK_ADJOINT=torch (the gathers + complex multiply-reduce the kernel replaces), same process, warm,
 median of `reps` wall-clock times after torch.cuda.synchronize(), and the peak allocated device memory of each path.  Also times the adjoint call alone (the
 eigen-chain under autograd is common to both paths).  One JSON line; --md prints the table of profiles/kspace_adjoint.md."""

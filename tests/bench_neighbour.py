@@ -1,4 +1,4 @@
-"""Micro-benchmark of the device neighbour list of HamGNN_pre.build_internal_graph (hamgnn_amd/internal_graph.py, hg_neighbour_* in csrc/aux_kernels.hip) on
+"""Micro-benchmark of the device neighbour list of HamGNN_pre.build_internal_graph (hamgnn_amd/internal_graph.py, hg_neighbour_* in csrc/neighbour.hip) on
 sio2_10k, at radius_scale 1.01 (the reference's config default) and 1.5 (and on sio2_3000 at 1.5, where the forward's edge rows stay below 2^31 elements):
   * the whole build (build_internal_graph: binning, count, prefix sum, fill, key sort, decode, matching, with its two read-backs), host clock around a
     device synchronise, median over `reps` after `warmup` builds;

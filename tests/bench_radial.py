@@ -1,4 +1,4 @@
-"""Micro-benchmark of hg_radial_hidden_multi (csrc/aux_kernels.hip): the 13 weight generators (64 -> 64 -> 64) of a 3-layer backbone on
+"""Micro-benchmark of hg_radial_hidden_multi (csrc/radial.hip): the 13 weight generators (64 -> 64 -> 64) of a 3-layer backbone on
 822 350 basis rows, one launch; checked against torch on a slice.  HG_LIB_PATH selects the .so."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

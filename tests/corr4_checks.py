@@ -1,5 +1,5 @@
 """Checks of the correlation-4 CorrProductBlock shared by tests/test_corr4_cpu.py (ops replaced by the stand-ins of tests/cpu_ops_corr.py) and
-tests/test_corr4_gpu.py (the HIP kernels of csrc/sym_contraction_nu.hip): forward and every gradient against the fp64 oracle (oracle/mace_ref.py) and
+tests/test_corr4_gpu.py (the HIP kernels of csrc/sym_contraction.hip): forward and every gradient against the fp64 oracle (oracle/mace_ref.py) and
 torch.autograd through it.  The oracle blocks are built once per (irreps, hidden channels) -- its dense U_4 takes seconds -- and never modified."""
 import contextlib
 import functools

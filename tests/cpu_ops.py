@@ -411,7 +411,7 @@ def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
 
 
 def w3_split_refill(w, se, so, dh, dl, scale, lo_scale):
-    """ops.w3_split_refill in torch ops (the arithmetic of csrc/aux_kernels.hip:w3_split_refill_kernel)"""
+    """ops.w3_split_refill in torch ops (the arithmetic of csrc/radial.hip:w3_split_refill_kernel)"""
     xe, xo = w[se] * scale, w[so] * scale
     he, ho = xe.half(), xo.half()
     le, lo = ((xe - he.float()) * lo_scale).half(), ((xo - ho.float()) * lo_scale).half()

@@ -1,4 +1,4 @@
-"""CPU stand-ins for the order-generic symmetric-contraction entry points (ops.sym_contraction_nu / sym_contraction_nu_backward, csrc/sym_contraction_nu.hip)
+"""CPU stand-ins for the order-generic symmetric-contraction entry points (ops.sym_contraction_nu / sym_contraction_nu_backward, csrc/sym_contraction.hip)
 -- TEST INFRASTRUCTURE in the style of tests/cpu_ops.py, never shipped.  They consume EXACTLY the tables the product hands to the kernels: the forward
 the nu-th CSR entry list of plan.sym_contraction_tables, the adjoint the two transposed tables of plan.sym_contraction_adjoint_tables (by component and
 by kappa), in float64.  `install(monkeypatch)` = cpu_ops.install + these two."""

@@ -429,7 +429,7 @@ def run_linear_tables(tabs, x, res=(), dtype=np.float64):
 
 
 def sym_contraction(tab, hp, z, W1, W2, C, out_dim):
-    """numpy twin of hg_sym_contraction (hamgnn_amd/csrc/head.hip): hp planar hidden rows [N, Dp]; W1 [nel, K1tot, C], W2 [nel, K2tot, C]"""
+    """numpy twin of hg_sym_contraction (hamgnn_amd/csrc/sym_contraction.hip): hp planar hidden rows [N, Dp]; W1 [nel, K1tot, C], W2 [nel, K2tot, C]"""
     N = hp.shape[0]
     out = np.zeros((N, out_dim), dtype=np.float64)
     x = np.stack([hp[:, tab["ell_off"] + c] for c in range(C)], axis=1)          # [N, C, num_ell]
@@ -449,7 +449,7 @@ def sym_contraction(tab, hp, z, W1, W2, C, out_dim):
 
 
 def sym_contraction3(tab, hp, z, W3, C, out):
-    """numpy twin of hg_sym_contraction3 (hamgnn_amd/csrc/corr3.hip): ADDS the nu = 3 term to the planar rows `out` [N, Dp] (float64 copy returned)"""
+    """numpy twin of hg_sym_contraction3 (hamgnn_amd/csrc/sym_contraction.hip): ADDS the nu = 3 term to the planar rows `out` [N, Dp] (float64 copy returned)"""
     out = np.array(out, dtype=np.float64)
     x = np.stack([hp[:, tab["ell_off"] + c] for c in range(C)], axis=1).astype(np.float64)     # [N, C, num_ell]
     ent, ptr = tab["ent3"], tab["ptr3"]

@@ -1,4 +1,4 @@
-"""Checks of HamGNN_pre.build_internal_graph (hamgnn_amd/internal_graph.py + the hg_neighbour_* kernels of csrc/aux_kernels.hip), shared by
+"""Checks of HamGNN_pre.build_internal_graph (hamgnn_amd/internal_graph.py + the hg_neighbour_* kernels of csrc/neighbour.hip), shared by
 tests/test_internal_graph_gpu.py (HIP kernels) and tests/test_internal_graph_cpu.py (host logic on the stand-ins of tests/cpu_ops.py + the numpy twin of the
 three neighbour-list entry points below, which follows the kernels' binning and loop structure).
 

@@ -1,6 +1,7 @@
 """ISA audit of a HIP source for gfx950 (the tool behind profiles/r03_*: "ISA audit" sections).
 
     python tests/isa_audit.py hamgnn_amd/csrc/tp_is.hip [-D FLAG ...] [--kernel SUBSTR] [--all]
+    python tests/isa_audit.py --diff OLD_CSRC NEW_CSRC      (a refactor left every kernel's device code as it was: see diff_device_code)
 
 Compiles the file with `hipcc --cuda-device-only -S`, splits every kernel into basic blocks and prints, per block, the sequence of its
 memory / MFMA instructions and waits:  M = v_mfma, G = global load, D = LDS-DMA / buffer load, W = global store / atomic, r / w = LDS
@@ -62,8 +63,46 @@ def kernels(text):
         if not name:
             continue
         g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", sec).group(1)) if re.search(r"\." + k + r":\s+(\d+)", sec) else -1
-        meta[name.group(1)] = dict(vgprs=g("vgpr_count"), vgpr_spills=g("vgpr_spill_count"), sgpr_spills=g("sgpr_spill_count"), scratch=g("private_segment_fixed_size"))
+        meta[name.group(1)] = dict(vgprs=g("vgpr_count"), vgpr_spills=g("vgpr_spill_count"), sgpr_spills=g("sgpr_spill_count"), scratch=g("private_segment_fixed_size"),
+                                   lds=g("group_segment_fixed_size"))
     return [k for k in out if any(ins for _, ins in k[1])], meta
+
+
+def device_code(csrc):
+    """{mangled kernel name: (source file, instruction list, metadata)} of every *.hip of a csrc directory.  Only what moving a kernel to another
+    file changes is normalised: the function index inside local labels (.LBB<n>_k, .LJTI<n>_k)."""
+    from concurrent.futures import ThreadPoolExecutor
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    with ThreadPoolExecutor(8) as pool:
+        texts = list(pool.map(lambda f: compile_to_asm(os.path.join(csrc, f)), files))
+    code = {}
+    for f, text in zip(files, texts):
+        ks, meta = kernels(re.sub(r"(\.L[A-Za-z]+)\d+_(\d+)", r"\1_\2", text))
+        for name, blocks in ks:
+            code[name] = (f, [i for lab, ins in blocks for i in [lab + ":"] + ins], meta.get(name, {}))
+    return code
+
+
+def diff_device_code(old_csrc, new_csrc):
+    """--diff: the kernels of two csrc trees, keyed by mangled name, must have equal instruction lists and equal register / spill / scratch / LDS
+    figures.  Prints one line per file of the new tree (kernels, instructions, differing kernels); returns the number of differences."""
+    old, new = device_code(old_csrc), device_code(new_csrc)
+    bad = sorted(set(old) ^ set(new))
+    for n in bad:
+        print(f"only in {'old' if n in old else 'new'}: {n}  ({(old.get(n) or new.get(n))[0]})")
+    per = {}
+    for n in sorted(set(old) & set(new)):
+        f, ins, meta = new[n]
+        same = ins == old[n][1] and meta == old[n][2]
+        k = per.setdefault(f, [0, 0, 0])
+        k[0] += 1; k[1] += sum(not i.endswith(":") for i in ins); k[2] += not same
+        if not same:
+            bad.append(n)
+            print(f"DIFFERS: {n}  {old[n][0]} -> {f}: {len(old[n][1])} -> {len(ins)} lines, {old[n][2]} -> {meta}")
+    for f, (nk, ni, nd) in sorted(per.items()):
+        print(f"{f:24s} kernels {nk:4d}  instructions {ni:8d}  differing {nd}")
+    print(f"total: kernels {sum(k[0] for k in per.values())}, instructions {sum(k[1] for k in per.values())}, differing {len(bad)}")
+    return len(bad)
 
 
 def seq_of(ins):
@@ -105,8 +144,11 @@ def audit(src, defines=(), kernel=None):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("src"); ap.add_argument("-D", action="append", default=[]); ap.add_argument("--kernel"); ap.add_argument("--all", action="store_true")
+    ap.add_argument("src", nargs="?"); ap.add_argument("-D", action="append", default=[]); ap.add_argument("--kernel"); ap.add_argument("--all", action="store_true")
+    ap.add_argument("--diff", nargs=2, metavar=("OLD_CSRC", "NEW_CSRC"), help="compare the device code of every kernel of two csrc directories")
     a = ap.parse_args()
+    if a.diff:
+        sys.exit(1 if diff_device_code(*a.diff) else 0)
     for k in audit(a.src, a.D, a.kernel):
         nm = sum(s.count("M") for _, _, s, _ in k["blocks"])
         ser = sum(len(m.group(0)) // 8 for _, _, s, _ in k["blocks"] for m in re.finditer(r"(r\[l\(0\)\]M){2,}", s))

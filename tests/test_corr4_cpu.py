@@ -1,6 +1,6 @@
 """`correlation: 4` on the CPU: the planner's nu = 4 tables and their transposes against the fp64 oracle (oracle/mace_ref.py) and autograd through it, and
 the product's host logic -- CorrProductBlock, a whole HamGNNConvE3 with use_corr_prod, a whole HamGNNTransformer -- on the table-exact stand-ins of
-tests/cpu_ops_corr.py.  The `-m gpu` twins (tests/test_corr4_gpu.py) run the same checks through the HIP kernels of csrc/sym_contraction_nu.hip.
+tests/cpu_ops_corr.py.  The `-m gpu` twins (tests/test_corr4_gpu.py) run the same checks through the HIP kernels of csrc/sym_contraction.hip.
 Bounds: the table-level checks run in float64 on fp32 coefficients and keep the 1e-6 of the nu <= 3 table tests (tests/test_plan_emu.py); everything
 that goes through the product's fp32 rows is held to G.TOL, as every parity test here.
 Every comparison with the oracle plans the nu = 4 table without the reference's natural-parity filter, as the oracle enumerates it (`oracle_paths`,

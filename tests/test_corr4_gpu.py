@@ -1,4 +1,4 @@
-"""-m gpu: `correlation: 4` through the order-generic HIP kernels of csrc/sym_contraction_nu.hip (hg_sym_contraction_nu / hg_sym_contraction_nu_backward)
+"""-m gpu: `correlation: 4` through the order-generic HIP kernels of csrc/sym_contraction.hip (hg_sym_contraction_nu / hg_sym_contraction_nu_backward)
 against the fp64 oracle and torch.autograd through it -- tolerance G.TOL (1e-5 relative, max-norm), the bound of every parity test here and of the
 nu = 3 backward tests -- plus bit-reproducibility of two launches, the opt-in HG_CORR_KERNEL=nu route against the default kernels (two evaluation orders
 of the same fp32 sums: G.SAME_MATH_TOL) and the reference's own correlation-4 block.  The CPU twins: tests/test_corr4_cpu.py.

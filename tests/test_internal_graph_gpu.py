@@ -1,4 +1,4 @@
-"""HamGNN_pre.build_internal_graph on the GPU: the periodic neighbour list of csrc/aux_kernels.hip (hg_neighbour_bin / _pairs / _decode) bit-equal to the host
+"""HamGNN_pre.build_internal_graph on the GPU: the periodic neighbour list of csrc/neighbour.hip (hg_neighbour_bin / _pairs / _decode) bit-equal to the host
 statement of the same rule (synthetic.build_graph on the fp32-rounded numbers), both backbones with the switch on against the same weights with the switch off
 on the host-built internal graph (no difference at all), against the fp64 oracle (gpu_checks.TOL), and one training step against autograd through the oracle
 (the bound of the existing full-model gradient tests).  Crystals, references and the margin assertion: tests/internal_graph_checks.py."""

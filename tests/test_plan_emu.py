@@ -620,7 +620,7 @@ def test_sym_contraction_nu3_term_vs_oracle_and_autograd(golden_dir):
     hp = torch.from_numpy(lay.to_planar(h.detach().numpy()))
     gp = torch.from_numpy(lay.to_planar(Gm.numpy()))
     low = torch.from_numpy(emu.sym_contraction(tab, hp.numpy(), z.numpy(), W1.numpy(), W2.numpy(), nh, lay.dim))
-    got = torch.from_numpy(emu.sym_contraction3(tab, hp.numpy(), z.numpy(), W3.numpy(), nh, low.numpy()))      # the table-exact twin of csrc/corr3.hip
+    got = torch.from_numpy(emu.sym_contraction3(tab, hp.numpy(), z.numpy(), W3.numpy(), nh, low.numpy()))      # the table-exact twin of csrc/sym_contraction.hip
     assert rel(lay.from_planar(got.numpy()), out.detach().numpy()) < 1e-6            # (the tables hold their coefficients in fp32)
     assert rel(got.numpy(), low.numpy()) > 1e-2                                       # the nu = 3 term is not negligible in this check
     g_h, gW1, gW2 = sym_contraction_backward(tab, hp, z, W1, W2, nh, gp, chunk=3)

@@ -1,4 +1,4 @@
-"""Training on `overlap` and `band_gap` targets on the GPU: hg_hk_assemble_adjoint (csrc/head.hip) alone against the fp64 torch adjoint, the head's backward
+"""Training on `overlap` and `band_gap` targets on the GPU: hg_hk_assemble_adjoint (csrc/kspace.hip) alone against the fp64 torch adjoint, the head's backward
 with ham_only=False and whole-model steps with `overlap` / `band_gap` / row-wise-metric losses against torch.autograd through the fp64 oracle.  Tolerances: the
 project's contract gpu_checks.TOL against fp64; the bars of the existing band-energy tests for everything behind the complex64 eigensolver."""
 import pytest

@@ -1,5 +1,5 @@
 """Shared checks of the training targets beyond the Hamiltonian (tests/test_train_targets_gpu.py on the GPU, tests/test_train_targets_cpu.py on the
-CPU stand-ins): the adjoint of the H(k) assembly (csrc/head.hip: hg_hk_assemble_adjoint) alone, `overlap` losses through a ham_only=False head,
+CPU stand-ins): the adjoint of the H(k) assembly (csrc/kspace.hip: hg_hk_assemble_adjoint) alone, `overlap` losses through a ham_only=False head,
 `band_gap` losses through the k-space chain, and the row-wise metrics.  All references are fp64: oracle.hamgnn_ref under torch.autograd, and the torch
 path of kspace.assemble_k_adjoint evaluated in fp64 on the CPU."""
 import math

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../hamgnn_amd/csrc"
 make -j8 > /dev/null
 mkdir -p ../lib/variants
 FILES=${HG_VARIANT_FILES:-tp_is}
-ALL="tp_fused tp_is tp_wgrad aux_kernels head attention linear linear_wgrad rowprog block_gemm corr3 kan sym_contraction_nu"
+ALL="tp_fused tp_is tp_wgrad geometry radial row_ops neighbour head kspace sym_contraction attention linear linear_wgrad rowprog block_gemm kan spectra"      # = SRCS of the Makefile
 for spec in "$@"; do
   name="${spec%%:*}"; flags="${spec#*:}"
   ( objs=""
