@@ -247,6 +247,17 @@ extern "C" int hg_gate_backward(const float* x, int64_t x_stride, const float* g
 // scaled by ssp(n) / n with n = sqrt(max(sum_a x_a^2, eps^2)).  chan_tab int32[nchan][2] = {offset of the channel's first component, component
 // stride (mulp) | ncomp << 16}; the channel-padding slots of a planar row (no table entry) are written as zeros.  One thread per (row, channel).
 __device__ __forceinline__ float hg_ssp(float x) { return (x > 20.f ? x : log1pf(__expf(x))) - 0.69314718055994531f; }
+// The two factors of the kernels below, ssp(n) / n and (sigmoid(n) - ssp(n) / n) / n.  log1pf(__expf(n)) and ln 2 are both 0.69 for small n and the difference
+// cancels (1.4e-5 of the scale at n = 1e-2, a scale of 0 instead of 0.5 at the clamp n = 1e-8), so below HG_SSP_SERIES the factors come from their series
+// ln(1 + e^n) = ln 2 + n/2 + n^2/8 - n^4/192 + ...: 1/2 + n/8 - n^3/192 (next term n^5/2880: 7e-9 of the value at the threshold) and 1/8 - n^2/64 (next term
+// n^4/576: 1e-6 of the factor, which scales a term that is n/4 of the gradient: 4e-8); above the threshold the direct form loses 1e-7 / (n/2), below 2e-6.
+#define HG_SSP_SERIES 0.1f
+__device__ __forceinline__ float hg_ssp_over_n(float n) {
+    return n < HG_SSP_SERIES ? fmaf(n, fmaf(n * n, -1.f / 192.f, 0.125f), 0.5f) : hg_ssp(n) / n;
+}
+__device__ __forceinline__ float hg_dssp_over_n(float n, float sc) {       // (sigmoid(n) - sc) / n with sc = hg_ssp_over_n(n)
+    return n < HG_SSP_SERIES ? fmaf(n * n, -1.f / 64.f, 0.125f) : (1.f / (1.f + __expf(-n)) - sc) / n;
+}
 __global__ void norm_act_kernel(const float* __restrict__ x, int64_t xs, const int2* __restrict__ chan_tab, int nchan, float eps2, int64_t rows,
                                 float* __restrict__ out, int64_t os) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -258,7 +269,7 @@ __global__ void norm_act_kernel(const float* __restrict__ x, int64_t xs, const i
     float n2 = 0.f;
     for (int a = 0; a < nc; ++a) n2 = fmaf(xr[a * st], xr[a * st], n2);
     n2 = n2 < eps2 ? eps2 : n2;
-    const float n = sqrtf(n2), sc = hg_ssp(n) / n;
+    const float n = sqrtf(n2), sc = hg_ssp_over_n(n);
     float* __restrict__ o = out + r * os + t.x;
     for (int a = 0; a < nc; ++a) o[a * st] = sc * xr[a * st];
 }
@@ -293,8 +304,8 @@ __global__ void norm_act_backward_kernel(const float* __restrict__ x, int64_t xs
     }
     const bool clamped = n2 < eps2;
     n2 = clamped ? eps2 : n2;
-    const float n = sqrtf(n2), s = hg_ssp(n), sc = s / n;
-    const float k = clamped ? 0.f : dot * (1.f / (1.f + __expf(-n)) - sc) / n2;
+    const float n = sqrtf(n2), sc = hg_ssp_over_n(n);
+    const float k = clamped ? 0.f : dot * hg_dssp_over_n(n, sc) / n;
     float* __restrict__ o = gx + r * gxs + t.x;
     for (int a = 0; a < nc; ++a) o[a * st] = fmaf(k, xr[a * st], sc * gr[a * st]);
 }
@@ -369,7 +380,7 @@ __global__ void embed_lookup_kernel(const float* __restrict__ Ta, const float* _
     float v = 0.f;
     if (t < T) {
         v = Ta[z[ia ? ia[r] : r] * T + t];
-        if (Tb) v += Tb[z[ib[r]] * T + t];
+        if (Tb) v += Tb[z[ib ? ib[r] : r] * T + t];
     }
     out[i] = v;
 }

@@ -247,7 +247,8 @@ int hg_from_planar(const float* xp, int64_t rows, int Dp, const int32_t* map, fl
 
 /* embedding source rows: out[e][t] = Ts[z[src[e]]][t] + Td[z[dst[e]]][t]   (PairInteractionEmbeddingBlock.forward,
  * hamgnn/nn/embeddings.py:325-326 with one-hot node attrs: the two o3.Linear are row look-ups);
- * idx_b == NULL => single table (chemical embedding AtomwiseLinear, toolbox/nequip/nn/_atomwise.py:55-57).           */
+ * Tb == NULL => single table (chemical embedding AtomwiseLinear, toolbox/nequip/nn/_atomwise.py:55-57); idx_a == NULL /
+ * idx_b == NULL => that table is indexed by the row itself (z[e]).                                                   */
 int hg_embed_lookup(const float* Ta, const float* Tb, const int64_t* z, const int64_t* idx_a, const int64_t* idx_b,
                     int64_t rows, int T, int Tp, float* out, void* stream);
 

@@ -235,9 +235,9 @@ def norm_act(x, chan_tab, eps=1e-8):
     for off, w in tab:
         st, nc = int(w) & 0xffff, int(w) >> 16
         cols = [int(off) + a * st for a in range(nc)]
-        v = x[:, cols]
+        v = x[:, cols].double()                                # in float64: softplus(n) - ln 2 cancels for small norms (in float32 the scale is 0 instead of 0.5 at the clamp)
         n = torch.sqrt(torch.clamp((v * v).sum(1), min=eps * eps))
-        out[:, cols] = v * ((torch.nn.functional.softplus(n) - math.log(2.0)) / n)[:, None]
+        out[:, cols] = (v * ((torch.nn.functional.softplus(n) - math.log(2.0)) / n)[:, None]).to(x.dtype)
     return out
 
 
