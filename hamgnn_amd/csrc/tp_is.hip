@@ -14,6 +14,9 @@
 // Items, fragments and weights are exactly those of the segment-stationary program (same planner output, regrouped).
 #include "tp_stage.h"
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) float* is_ldsp;           // an operand pointer that is an LDS address by TYPE (32 bits; ds_read whatever the optimiser infers)
+
 #ifdef HG_PROF
 __device__ unsigned long long hg_prof_is_acc[16];              // the phase times of this kernel (hg_device.h: HG_T), read by hg_prof_is_read
 #endif
@@ -195,9 +198,11 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
                         mid[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][q], bv[c][q], mid[rt][c], 0, 0, 0);
         }
     } else {                                                   // natural K: element (c, 4 sl + g) = piece cbase + sl, component g
-        const float* __restrict__ pc[NC];
+        // (LDS pointers by type: as generic pointers the paired reads lost their address space in 17 of the 30 instantiations -- flat loads, 64-bit address
+        //  arithmetic; the single reads before them had in one: 60 flat_load_dword)
+        is_ldsp pc[NC];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) pc[c] = stage + so0 + (c0p + IS_COL(c) * cdir) * 64 + el * 4 + g;
+        for (int c = 0; c < NC; ++c) pc[c] = (is_ldsp)(stage + so0 + (c0p + IS_COL(c) * cdir) * 64 + el * 4 + g);
 #pragma unroll
         for (int rt = 0; rt < RTM; ++rt) av_n[rt] = aw[rt * 64];
         int nq = ksteps;                                       // K-steps left in this source (>= 4 except in its tail group)
@@ -215,20 +220,35 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
 #pragma unroll
                 for (int rt = 0; rt < RTM; ++rt) av_n[rt] = aw[((t + 1) * RTM + rt) * 64];
             }
+            // the operands of K-steps q and q + 1 in ONE LDS instruction per column (ds_read2st64_b32: pieces q and q + 1 of the column's component are 64 dwords
+            // apart) and one wait per pair: half the LDS instructions and waits of a read per K-step, same operands, same K order.  An odd piece count leaves a last
+            // step without a partner: its read brings the next piece of the staged image along -- the next component's first piece or, behind the last component,
+            // the padding of this source's own image (an odd piece count never fills its last group of four pieces: asserted in plan/schedule_is.py) -- which no
+            // MFMA is issued for.
+            // The NC reads stay together ahead of the MFMAs: left alone, the scheduler of the one-row-tile instantiations read every operand into ONE
+            // register right before its MFMA -- an LDS round trip per MFMA (ISA audit of r4: 334 static MFMAs in such chains)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < 4; q += 2) {
                 if (q < nq) {
-                    float b[NC];
+                    f32x2 b[NC];
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) b[c] = pc[c][q * 64];
-                    // the NC operand reads stay together ahead of the MFMAs: left alone, the scheduler of the one-row-tile instantiations read every
-                    // operand into ONE register right before its MFMA -- an LDS round trip per MFMA (ISA audit: 334 of 4 096 static MFMAs)
+                    for (int c = 0; c < NC; ++c) {
+                        b[c][0] = pc[c][q * 64];
+                        b[c][1] = pc[c][q * 64 + 64];
+                    }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int rt = 0; rt < RTM; ++rt)
 #pragma unroll
                         for (int c = 0; c < NC; ++c)
-                            mid[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][q], b[c], mid[rt][c], 0, 0, 0);
+                            mid[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][q], b[c][0], mid[rt][c], 0, 0, 0);
+                    if (q + 1 < nq) {
+#pragma unroll
+                        for (int rt = 0; rt < RTM; ++rt)
+#pragma unroll
+                            for (int c = 0; c < NC; ++c)
+                                mid[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][q + 1], b[c][1], mid[rt][c], 0, 0, 0);
+                    }
                 }
             }
             nq -= 4;

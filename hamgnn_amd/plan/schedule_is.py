@@ -429,6 +429,10 @@ def _is_schedule_part(prog: "Program", members: List[int], hp4: int, seg_base: i
             raise NotImplementedError("static-stream schedule: an input block whose items use both radial weight generators")
         b["cls"] = cls.pop() if len(cls) == 1 else None        # None: plain Linear items only (no radial scale) / not separated
         b["src_floats"] = ceil_div((2 * b["li"] + 1) * (b["in_mulp"] // 4), 4) * 256
+        # csrc/tp_is.hip reads GEMM1's natural-K operands two K-steps at a time: with an odd piece count per component the last read of a component brings the
+        # NEXT piece of the image along (unused).  Behind the last component that piece must still lie inside this source's image: an odd count of odd-sized
+        # components never fills its last group of four pieces
+        assert (b["in_mulp"] // 4) % 2 == 0 or b["src_floats"] > (2 * b["li"] + 1) * (b["in_mulp"] // 4) * 64
         b["floats"] = b["nsrc"] * b["src_floats"]
         if b["floats"] > stage_floats:
             raise NotImplementedError(f"input-stationary schedule: LDS staging area of {stage_floats * 4} B is smaller than an input block")
