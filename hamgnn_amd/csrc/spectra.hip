@@ -2,6 +2,7 @@
 //   hg_mulliken_weights: per-state Mulliken weights of orbital groups, w[s, g] = wk[s] * sum_{mu in g} Re(conj(c_mu) (S c)_mu)
 //   hg_dos_broaden:      D[j, g] = sum_s A(E_j, eps_s) W[s, g], A a normalised Gaussian: a GEMM whose left operand is generated in registers
 //   hg_dos_tetra:        the same GEMM with the linear tetrahedron method's corner weights (DOS or number of states) as the left operand
+//   hg_bond_weights:     per-state bond weights (COOP / COHP), w[s, g] = wk[s] * sum_{bonds of g} Re(phase c_i^+ X_bond c_j) from the real-space rows
 // No atomics, no claim-order reduction: all kernels are bit-reproducible from launch to launch.  Callers allocate everything.
 #include "hg_device.h"
 
@@ -381,4 +382,143 @@ extern "C" int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, in
         dos_tetra_kernel<false><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner,
                                                                                           band_lo, band_hi, E0, dE, ne, mode, accumulate ? 1 : 0, D);
     return hg_check_launch("hg_dos_tetra");
+}
+
+// ------------------------------------------------------------------------------------------------ bond-resolved weights (COOP / COHP)
+// W[s, 1 + g] = wk[s] * (sum_{e in edges(g)} t_e(s) + sum_{i in atoms(g)} o_i(s)),  t_e(s) = Re(exp(2 pi i k_s . shift_e) c_i^+ X_off[e] c_j), o_i(s) =
+// Re(c_i^+ X_on[i] c_i), (i, j) = (erow[e], ecol[e]) the row and column atom of hg_hk_assemble, c_i the entries ooff[i] + orank[i][a] of row s of C.
+// One workgroup owns one (tile of 16 states, group); the group's members -- its edges in the order of eidx, then its atoms in the order of aidx -- are
+// dealt to the 4 waves in contiguous quarters.  Per member a wave forms T = X C_j for its 16 states as two real GEMMs (X times Re C_j and Im C_j) on
+// v_mfma_f32_16x16x4_f32 over the nao x nao block as it lies in the row: row tiles of 16 orbitals a (NT of them, 2 NT independent accumulators), steps of 4
+// orbitals b; lane l holds A[a = 16 t + (l & 15)][b = 4 step + (l >> 4)] = X[a][b] and B[b][state l & 15] = C[s][ooff[j] + orank[j][b]].  Orbitals an atom
+// does not have (orank < 0) and the tails past nao go by predication: their A and B elements are 0 and nothing is read for them (the load is redirected
+// to element 0 and its value dropped), so rectangular blocks need no padded input.  Then per lane sum_a conj(C_i[a]) T[a] over its rows a = 16 t + 4 (l >> 4)
+// + r (C/D map of the tile), two shuffles add the four lane quarters, the phase (k . shift and sincos in double, rounded once, as hk_pairs_kernel) turns the
+// complex sum into t_e, and the member is added to the wave's running sum.  The waves' sums are added through LDS as ((w0 + w1) + w2) + w3: one owner per
+// output element, a fixed order, no atomics.  The extra workgroups g = G write column 0 (= wk) and the pad columns (= 0); an empty group writes 0.  A state
+// row past ns repeats row ns - 1 and is not stored; the phase is per state, so the states of a tile may belong to different k-points, and a row of W does
+// not depend on which other states the launch holds.  Every table entry is clamped into range before it indexes anything.
+template <int NT>
+__global__ __launch_bounds__(256) void bond_weights_kernel(const float2* __restrict__ Cm, int ns, int M, const int32_t* __restrict__ kidx,
+                                                           const float* __restrict__ kvec, int nk, const float* __restrict__ X_on,
+                                                           const float* __restrict__ X_off, const int32_t* __restrict__ erow,
+                                                           const int32_t* __restrict__ ecol, const float* __restrict__ shift, int E, int n_atoms, int nao,
+                                                           const int32_t* __restrict__ orank, const int32_t* __restrict__ ooff,
+                                                           const int32_t* __restrict__ eptr, const int32_t* __restrict__ eidx,
+                                                           const int32_t* __restrict__ aptr, const int32_t* __restrict__ aidx, int G, int Gp, int ntile,
+                                                           const float* __restrict__ wk, float* __restrict__ W) {
+    __shared__ float part[4][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = blockIdx.x / ntile, s0 = 16 * (blockIdx.x - g * ntile);
+    if (g == G) {                                              // (block-uniform) column 0 and the pad columns 1 + G .. Gp - 1 of the tile's rows
+        const int nc = Gp - G;
+        for (int q = threadIdx.x; q < 16 * nc; q += 256) {
+            const int r = q / nc, c = q - r * nc, s = s0 + r;
+            if (s < ns) W[(int64_t)s * Gp + (c == 0 ? 0 : G + c)] = c == 0 ? wk[s] : 0.f;
+        }
+        return;
+    }
+    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
+    const int sl = lane & 15, kq = lane >> 4;
+    const int sc = s0 + sl < ns ? s0 + sl : ns - 1;
+    const float2* __restrict__ c = Cm + (int64_t)sc * M;
+    const int kp = clampi(kidx[sc], nk);
+    const double kx = kvec[3 * kp], ky = kvec[3 * kp + 1], kz = kvec[3 * kp + 2];
+    const int e0 = eptr[g], a0 = aptr[g];
+    const int ne = E > 0 && eptr[g + 1] > e0 ? eptr[g + 1] - e0 : 0, na = aptr[g + 1] > a0 ? aptr[g + 1] - a0 : 0;
+    const int nm = ne + na, chunk = (nm + 3) >> 2;
+    const int m0 = wave * chunk, m1 = m0 + chunk < nm ? m0 + chunk : nm;
+    const int nao2 = nao * nao;
+    float sum = 0.f;
+    for (int m = m0; m < m1; ++m) {                            // (wave-uniform bounds and member: every lane reaches every MFMA and shuffle)
+        const bool edge = m < ne;
+        int i, j;
+        const float* __restrict__ X;
+        float cf = 1.f, sf = 0.f;
+        if (edge) {
+            const int e = clampi(eidx[e0 + m], E);
+            i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+            X = X_off + (int64_t)e * nao2;
+            // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
+            const double ph = 6.283185307179586 * (kx * shift[3 * (int64_t)e] + ky * shift[3 * (int64_t)e + 1] + kz * shift[3 * (int64_t)e + 2]);
+            double sd, cd;
+            sincos(ph, &sd, &cd);
+            cf = (float)cd, sf = (float)sd;
+        } else {
+            i = j = clampi(aidx[a0 + (m - ne)], n_atoms);
+            X = X_on + (int64_t)i * nao2;
+        }
+        const int32_t* __restrict__ ri = orank + (int64_t)i * nao;
+        const int32_t* __restrict__ rj = orank + (int64_t)j * nao;
+        const int oi = ooff[i], oj = ooff[j];
+        int ra[NT];                                            // rank of this lane's A row a = 16 t + sl, or -1
+        f32x4 tr[NT], ti[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int a = 16 * t + sl;
+            ra[t] = ri[a < nao ? a : 0];
+            ra[t] = a < nao ? ra[t] : -1;
+            tr[t] = f32x4{0.f, 0.f, 0.f, 0.f}, ti[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        for (int b0 = 0; b0 < nao; b0 += 4) {
+            const int b = b0 + kq;
+            int rb = rj[b < nao ? b : 0];
+            rb = b < nao ? rb : -1;
+            float2 cj = c[clampi(oj + rb, M)];
+            cj = rb >= 0 ? cj : make_float2(0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bool ok = ra[t] >= 0 && rb >= 0;
+                float x = X[ok ? (16 * t + sl) * nao + b : 0];
+                x = ok ? x : 0.f;
+                tr[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.x, tr[t], 0, 0, 0);
+                ti[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.y, ti[t], 0, 0, 0);
+            }
+        }
+        float pr = 0.f, pi = 0.f;                              // sum_a conj(c_i[a]) T[a] over this lane's rows: C/D map row = 4 (lane >> 4) + r, column = state
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int a = 16 * t + 4 * kq + r;
+                int rr = ri[a < nao ? a : 0];
+                rr = a < nao ? rr : -1;
+                float2 ci = c[clampi(oi + rr, M)];
+                ci = rr >= 0 ? ci : make_float2(0.f, 0.f);
+                pr = fmaf(ci.y, ti[t][r], fmaf(ci.x, tr[t][r], pr));
+                pi = fmaf(-ci.y, tr[t][r], fmaf(ci.x, ti[t][r], pi));
+            }
+        pr += __shfl_xor(pr, 16, 64), pi += __shfl_xor(pi, 16, 64);
+        pr += __shfl_xor(pr, 32, 64), pi += __shfl_xor(pi, 32, 64);
+        sum += fmaf(cf, pr, -(sf * pi));                       // Re(phase * sum); an on-site member has phase 1
+    }
+    if (kq == 0) part[wave][sl] = sum;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        const int s = s0 + (int)threadIdx.x;
+        if (s < ns) W[(int64_t)s * Gp + 1 + g] = wk[s] * (((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x]);
+    }
+}
+
+extern "C" int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t* kidx, const float* kvec, int nk, const float* X_on, const float* X_off,
+                               const int32_t* erow, const int32_t* ecol, const float* shift, int64_t n_edges, int n_atoms, int nao, const int32_t* orank,
+                               const int32_t* ooff, const int32_t* eptr, const int32_t* eidx, const int32_t* aptr, const int32_t* aidx, int G, int Gp,
+                               const float* wk, float* W, void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (ns <= 0) return 0;
+    const int64_t ntile = (ns + 15) / 16;
+    if (M <= 0 || nk <= 0 || n_atoms <= 0 || nao <= 0 || nao > 48 || n_edges < 0 || n_edges > 2147483647LL || G < 0 || Gp < 1 + G || ns > 2147483647LL - 16 ||
+        ntile * ((int64_t)G + 1) > 2147483647LL)
+        return hg_fail(-2, "hg_bond_weights: bad sizes (M, nk, n_atoms >= 1, 1 <= nao <= 48, Gp >= 1 + G, ceil(ns / 16) (G + 1) < 2^31)");
+    if (!C || !kidx || !kvec || !X_on || !orank || !ooff || !eptr || !aptr || !wk || !W || (n_edges > 0 && (!X_off || !erow || !ecol || !shift)))
+        return hg_fail(-2, "hg_bond_weights: null pointer");
+    const dim3 grid((unsigned)(ntile * ((int64_t)G + 1)));
+#define HG_BOND_LAUNCH(NT_)                                                                                                                               \
+    bond_weights_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, kidx, kvec, nk, X_on, X_off, erow, ecol, shift, (int)n_edges, \
+                                                                     n_atoms, nao, orank, ooff, eptr, eidx, aptr, aidx, G, Gp, (int)ntile, wk, W)
+    if (nao <= 16) HG_BOND_LAUNCH(1);
+    else if (nao <= 32) HG_BOND_LAUNCH(2);
+    else HG_BOND_LAUNCH(3);
+#undef HG_BOND_LAUNCH
+    return hg_check_launch("hg_bond_weights");
 }

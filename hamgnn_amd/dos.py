@@ -22,6 +22,9 @@ Next to the Gaussians, the linear tetrahedron method (no width parameter; band e
 HIP kernel `hg_dos_tetra` (the same GEMM as the broadening with another generator for the left operand; band chunks can be added in turn), or torch ops (CPU
 tensors, HG_DOS=torch; the baseline of tests/bench_dos_tetra.py).  The formulas and the rule for flat tetrahedra stand in `tetra_dos`'s docstring.
 
+Bond-resolved weights (COOP / COHP / ICOHP: which bonds the states are in) come from hamgnn_amd/bonds.py: `bonds.bond_weights` writes rows in the same
+[ns, Gp] layout from the real-space rows and the eigenvectors, and `broaden`, `tetra_dos` and `tetra_states` take them unchanged.
+
 NOT built: the driver from saved Hamiltonian rows (assembly of H(k) / S(k), solver, these steps, per crystal and k-chunk).  Its one run at a realistic size
 (64 Si atoms, M = 832) ended in a GPU launch failure whose cause was not found, so it was taken out with its tests: profiles/dos.md."""
 from __future__ import annotations

@@ -988,6 +988,56 @@ def dos_tetra(eps, W, tet, kt, band_lo, band_hi, E0, dE, ne, mode=0, D=None, acc
 
 
 @_on_tensor_device
+def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, eptr, eidx, aptr, aidx, wk, Gp):
+    """W [ns, Gp] fp32 of bond groups from the eigenvector rows C_ [ns, M] complex64 and the real-space rows X_on [N, nao^2] / X_off [E, nao^2]: column 0 =
+    wk, column 1 + g = wk * (sum of Re(phase c_i^+ X_off[e] c_j) over the edges eidx[eptr[g]:eptr[g + 1]] + sum of Re(c_i^+ X_on[i] c_i) over the atoms
+    aidx[aptr[g]:aptr[g + 1]]), pad columns 0 (see include/hamgnn_hip.h:hg_bond_weights); every element is written.  kidx int32 [ns] -> rows of kvec
+    [nk, 3]; erow / ecol int32 [E], shift [E, 3]; orank int32 [N, nao], ooff int32 [N].  All tables are checked here, on the host, before the launch."""
+    _require_gpu(C_)
+    if C_.dim() != 2 or C_.dtype != torch.complex64:
+        raise ValueError(f"bond_weights: C must be complex64 [ns, M], got {C_.dtype} {tuple(C_.shape)}")
+    if not C_.is_contiguous():
+        raise ValueError("bond_weights: C must be contiguous (a sliced tensor would be read with the wrong stride)")
+    ns, M = int(C_.shape[0]), int(C_.shape[1])
+    if orank.dim() != 2 or orank.dtype != torch.int32:
+        raise ValueError(f"bond_weights: orank must be int32 [N, nao], got {orank.dtype} {tuple(orank.shape)}")
+    N, nao = int(orank.shape[0]), int(orank.shape[1])
+    E, nk, G = int(X_off.shape[0]), int(kvec.shape[0]), int(eptr.shape[0]) - 1
+    f32s = {"kvec": (kvec, (nk, 3)), "X_on": (X_on, (N, nao * nao)), "X_off": (X_off, (E, nao * nao)), "shift": (shift, (E, 3)), "wk": (wk, (ns,))}
+    i32s = {"kidx": (kidx, (ns,)), "erow": (erow, (E,)), "ecol": (ecol, (E,)), "ooff": (ooff, (N,)), "eptr": (eptr, (G + 1,)), "aptr": (aptr, (G + 1,)),
+            "eidx": (eidx, (int(eidx.numel()),)), "aidx": (aidx, (int(aidx.numel()),)), "orank": (orank, (N, nao))}
+    for dt, group in ((torch.float32, f32s), (torch.int32, i32s)):
+        for name, (t, shape) in group.items():
+            if t.dtype != dt or tuple(t.shape) != shape:
+                raise ValueError(f"bond_weights: {name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"bond_weights: {name} must be contiguous")
+            if t.device != C_.device:
+                raise ValueError(f"bond_weights: {name} is on {t.device}, C on {C_.device}")
+    if G < 0 or Gp < 1 + G:
+        raise ValueError(f"bond_weights: Gp = {Gp} holds no room for the state weight and {G} groups")
+    if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
+        raise ValueError(f"bond_weights: needs at least one atom, one k-point and one orbital and nao <= 48, got N = {N}, nk = {nk}, M = {M}, nao = {nao}")
+
+    def in_range(name, t, n):                                  # (host checks of the index tables: a device-to-host copy of two scalars each)
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError(f"bond_weights: {name} has entries outside [0, {n})")
+    in_range("kidx", kidx, nk), in_range("erow", erow, N), in_range("ecol", ecol, N), in_range("eidx", eidx, E), in_range("aidx", aidx, N)
+    for name, p, idx in (("eptr", eptr, eidx), ("aptr", aptr, aidx)):
+        ph = p.cpu()
+        if int(ph[0]) != 0 or int(ph[-1]) != idx.numel() or bool((ph[1:] < ph[:-1]).any()):
+            raise ValueError(f"bond_weights: {name} must ascend from 0 to the {idx.numel()} entries of its index list")
+    top = torch.where(orank >= 0, ooff[:, None] + orank, torch.zeros_like(orank))
+    if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
+        raise ValueError(f"bond_weights: orank / ooff point outside the {M} compact orbitals of C")
+    W = torch.empty(ns, Gp, device=C_.device, dtype=torch.float32)
+    check(lib().hg_bond_weights(ptr(torch.view_as_real(C_)), i64(ns), i32(M), ptr(kidx), ptr(kvec), i32(nk), ptr(X_on), ptr(X_off), ptr(erow), ptr(ecol),
+                                ptr(shift), i64(E), i32(N), i32(nao), ptr(orank), ptr(ooff), ptr(eptr), ptr(eidx), ptr(aptr), ptr(aidx), i32(G), i32(Gp),
+                                ptr(wk), ptr(W), _stream()), "hg_bond_weights")
+    return W
+
+
+@_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""
     _require_gpu(H)

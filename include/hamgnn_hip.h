@@ -468,6 +468,27 @@ int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, int Gp, const
                  const int32_t* kt_tet, const int32_t* kt_corner, const float* band_lo, const float* band_hi, double E0, double dE, int ne,
                  int mode, int accumulate, float* D, void* stream);
 
+/* Bond-resolved state weights of one crystal (COOP with overlap rows, COHP with Hamiltonian rows; csrc/spectra.hip), in the [ns][Gp] layout
+ * hg_dos_broaden and hg_dos_tetra consume.  C [ns][M] complex64 as (re, im) pairs: eigenvector rows in the compact orbital order of hg_hk_assemble,
+ * mu(i, a) = ooff[i] + orank[i][a] (orank int32 [n_atoms][nao], -1: atom i lacks orbital a; ooff int32 [n_atoms]); state s sits at k-point
+ * kvec[kidx[s]] (kvec fp32 [nk][3], kidx int32 [ns]).  X_on [n_atoms][nao^2], X_off [n_edges][nao^2] fp32: the real-space rows hg_hk_assemble takes;
+ * edge e couples row atom erow[e] to column atom ecol[e] with phase exp(2 pi i k . shift[e]) (shift fp32 [n_edges][3], in the unit dual to kvec).
+ *   t_e(s) = Re(exp(2 pi i k_s . shift_e) sum_{a, b} conj(C[s][mu(i, a)]) X_off[e][a][b] C[s][mu(j, b)]),  o_i(s) = the same with X_on[i], j = i, phase 1
+ *   (sums over the orbitals both atoms have);
+ *   W[s][0] = wk[s] exactly;  W[s][1 + g] = wk[s] * (sum_{q in [eptr[g], eptr[g+1])} t_{eidx[q]}(s) + sum_{q in [aptr[g], aptr[g+1])} o_{aidx[q]}(s));
+ *   W[s][1 + G ..] = 0.  Every element of W is written; an empty group gives 0.
+ * One workgroup per (16 states, group): the members (edges in eidx's order, then atoms in aidx's) go to 4 waves in contiguous quarters; per member
+ * X C_j is two real GEMMs on v_mfma_f32_16x16x4_f32 (row tiles of 16 orbitals, steps of 4, tails and missing orbitals by predication), then
+ * conj(C_i) . T over the rows, the phase (k . shift and sincos in double, rounded once) and the running sum; the waves add as ((w0 + w1) + w2) + w3.
+ * No atomics: two launches are bit-identical, and a row of W does not depend on the other rows of the launch.  Table entries are clamped into range
+ * before use; the caller checks them.  ns <= 0: returns 0 without a launch.  Refused (-2): M, nk or n_atoms < 1, nao < 1 or > 48, n_edges < 0,
+ * G < 0, Gp < 1 + G, ns > 2^31 - 17, ceil(ns / 16) (G + 1) >= 2^31, a null pointer where the sizes are not empty (eidx / aidx may be null when
+ * no group has an edge / an atom).                                                                                                          */
+int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t* kidx, const float* kvec, int nk, const float* X_on, const float* X_off,
+                    const int32_t* erow, const int32_t* ecol, const float* shift, int64_t n_edges, int n_atoms, int nao, const int32_t* orank,
+                    const int32_t* ooff, const int32_t* eptr, const int32_t* eidx, const int32_t* aptr, const int32_t* aidx, int G, int Gp,
+                    const float* wk, float* W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
