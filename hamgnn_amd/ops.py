@@ -2,6 +2,8 @@
 Every function launches hand-written HIP kernels from libhamgnn_hip.so; nothing falls back to torch arithmetic."""
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
 import math
 import os
@@ -11,11 +13,7 @@ import numpy as np
 import torch
 
 from . import plan as P
-from ._lib import check, f32, i32, i64, lib, ptr
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._lib import call, strided
 
 
 def _on_tensor_device(fn):
@@ -65,6 +63,53 @@ def _require_gpu(t: torch.Tensor):
         raise RuntimeError("hamgnn_amd: the MI355X hot path needs CUDA(ROCm) tensors; there is no CPU fallback")
 
 
+PROFILE_EVENTS = None        # bench.py sets this to a list: (start, end, rows, tag) HIP event pairs around the launches of linear_planar, tp_fused and row_program
+_NOT_PROFILED = contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _event_pair(rows, tag):
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()                                       # torch's current stream == the launch stream (_lib.call)
+    yield
+    ev1.record()
+    PROFILE_EVENTS.append((ev0, ev1, rows, tag))
+
+
+def _profiled(rows, tag):
+    """context of one launch: a HIP event pair around it on PROFILE_EVENTS while bench.py collects them"""
+    return _NOT_PROFILED if PROFILE_EVENTS is None else _event_pair(rows, tag)
+
+
+def _residuals(res):
+    """(res0, res0_stride, res1, res1_stride) of up to two residual row tensors: pointer and row stride each (column windows of wider rows pass as they
+    are), NULL and 0 where there is none"""
+    args = []
+    for r in (*res, None, None)[:2]:
+        args += [strided(r), r.stride(0) if r is not None else 0]
+    return args
+
+
+def _row_slots(ts):
+    """(tensors, host array of their row strides) of up to four row tensors by slot, None and 0 for a slot not in use: `src` / `src_stride` and `src_idx` of the
+    edge kernels (the typed call turns the tensors into the array of pointers and checks each as a strided() argument)"""
+    ts = (*ts, None, None, None, None)[:max(4, len(ts))]
+    return ts, (C.c_int64 * 4)(*[t.stride(0) if t is not None else 0 for t in ts])
+
+
+_NO_WIG_OFF = (C.c_int * 8)()
+
+
+def _wigner(geo):
+    """(wig, nW, wig_off) of a geometry, or NULL, 0 and zero offsets for launches that do not rotate"""
+    return (geo.wig, geo.nW, geo.wig_off) if geo is not None else (None, 0, _NO_WIG_OFF)
+
+
+def _hcache(geo) -> dict:
+    """the per-forward cache of hidden radial rows on a geometry object"""
+    return geo.__dict__.setdefault("_hcache", {})
+
+
 S_SPLIT_OFF = os.environ.get("HG_S_SPLIT", "1") == "0"      # A/B switch: the fp32 form of the radial scale (16 fp32 MFMAs per row tile instead of 6 half-precision ones)
 W3_SPLIT_PENDING: list = []     # (DeviceProgram, device scalar max |W3|) of refreshed programs whose half-precision range check is still to be read (check_w3_split)
 REPLAY_SPLIT = False         # set by graph_capture.CapturedForward while it warms up and captures: launches of the smallest crystals take the finer 2d split
@@ -80,10 +125,9 @@ def check_build_config():
     global _BUILD_CONFIG_OK
     if _BUILD_CONFIG_OK:
         return
-    L = lib()
     want = {0: ("HG_IS_WAVES", P.IS_WAVES), 1: ("HG_LITE_WAVES", P.IS_WAVES_LITE), 2: ("HG_LITE_SRING", P.LITE_SRING)}
     for what, (name, val) in want.items():
-        got = int(L.hg_build_config(what))
+        got = call("hg_build_config", what)
         if got != int(val):
             raise RuntimeError(f"{name}={val} does not match the loaded library (compiled with {got}): rebuild the variant or unset the variable")
     _BUILD_CONFIG_OK = True
@@ -92,10 +136,8 @@ def check_build_config():
 def w3_split_refill(w: torch.Tensor, se, so, dh, dl, scale: float, lo_scale: float) -> torch.Tensor:
     """the split-half-precision twins of the fp32 W3 blocks of the packed weight blob `w`, rewritten IN PLACE by one launch (csrc/radial.hip:hg_w3_split_refill; index
     tensors: DeviceProgram.refresh_w3_split); returns the device scalar max |w 2^s| for the lazy range check (check_w3_split)"""
-    _require_gpu(w)
-    assert w.dtype == torch.float32 and w.is_contiguous() and all(t.dtype == torch.int64 and t.is_contiguous() for t in (se, so, dh, dl))
     mx = torch.empty(1, device=w.device, dtype=torch.float32)
-    check(lib().hg_w3_split_refill(ptr(w), ptr(se), ptr(so), ptr(dh), ptr(dl), i64(se.numel()), C.c_float(scale), C.c_float(lo_scale), ptr(mx), _stream()), "hg_w3_split_refill")
+    call("hg_w3_split_refill", w, se, so, dh, dl, se.numel(), scale, lo_scale, mx)
     return mx[0]
 
 
@@ -233,24 +275,13 @@ class DeviceLinear:
 @_on_tensor_device
 def linear_planar(dl: DeviceLinear, x: torch.Tensor, res: Sequence[Optional[torch.Tensor]] = (), tag: str = "linear") -> torch.Tensor:
     """o3.Linear on planar rows, one streaming pass (csrc/linear.hip); res: up to two residual row tensors (output layout) added on the way"""
-    _require_gpu(x)
     rows = int(x.shape[0])
-    assert x.shape[1] == dl.in_dim and x.stride(1) == 1
+    assert x.shape[1] == dl.in_dim
     res = [r for r in res if r is not None]
-    assert len(res) <= 2
-    for r in res:
-        assert r.shape == (rows, dl.out_dim) and r.stride(1) == 1
+    assert len(res) <= 2 and all(r.shape == (rows, dl.out_dim) for r in res)
     out = torch.empty(rows, dl.out_dim, device=x.device, dtype=torch.float32)         # every column is written, padding included
-    if PROFILE_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().hg_linear_planar(ptr(x), i64(x.stride(0)), ptr(dl.items), i32(dl.nitems), ptr(dl.units), ptr(dl.paths), ptr(dl.weights),
-                                 C.c_void_p(res[0].data_ptr() if res else 0), i64(res[0].stride(0) if res else 0),
-                                 C.c_void_p(res[1].data_ptr() if len(res) > 1 else 0), i64(res[1].stride(0) if len(res) > 1 else 0),
-                                 i64(rows), ptr(out), i64(dl.out_dim), _stream()), "hg_linear_planar")
-    if PROFILE_EVENTS is not None:
-        ev1.record()
-        PROFILE_EVENTS.append((ev0, ev1, rows, tag))
+    with _profiled(rows, tag):
+        call("hg_linear_planar", x, x.stride(0), dl.items, dl.nitems, dl.units, dl.paths, dl.weights, *_residuals(res), rows, out, dl.out_dim)
     return out
 
 
@@ -292,16 +323,15 @@ def linear_wgrad_tables(irreps_in, irreps_out, device):
 def linear_wgrad(irreps_in, irreps_out, x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
     """d sum(y * gy) / d weight of an o3.Linear in e3nn's flat layout, all paths in ONE launch of csrc/linear_wgrad.hip + a fixed-order sum over
     the row chunks (x, gy: planar rows of the Linear's input and of the gradient of its output)"""
-    _require_gpu(x)
+    _require_gpu(x)                # (ahead of the return that launches nothing)
     units, nunits, gather, scale = linear_wgrad_tables(irreps_in, irreps_out, x.device)
     if nunits == 0:
         return x.new_zeros(0)
     rows = int(x.shape[0])
-    assert gy.shape[0] == rows and x.stride(1) == 1 and gy.stride(1) == 1
-    assert x.dtype == torch.float32 and gy.dtype == torch.float32, "hg_linear_wgrad reads fp32 rows (raw pointers: any other dtype would be misread)"
+    assert gy.shape[0] == rows
     nchunk = (rows + LW_ROWS - 1) // LW_ROWS
     part = torch.empty(nchunk, nunits * 1024, device=x.device, dtype=torch.float32)
-    check(lib().hg_linear_wgrad(ptr(x), i64(x.stride(0)), ptr(gy), i64(gy.stride(0)), i64(rows), ptr(units), i32(nunits), ptr(part), _stream()), "hg_linear_wgrad")
+    call("hg_linear_wgrad", x, x.stride(0), gy, gy.stride(0), rows, units, nunits, part)
     return part.sum(0)[gather] * scale
 
 
@@ -325,9 +355,8 @@ def use_block_gemm(t: torch.Tensor) -> bool:
 
 def block_gemm(bg: BlockGemm, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     """c[c_off + m * c_ld + n] = scale * sum_k op(a)[m, k] op(b)[k, n] for every unit of `bg` (a, b: flat fp32; c: flat fp32 or fp64, written in place)"""
-    _require_gpu(a)
-    assert a.dtype == torch.float32 and b.dtype == torch.float32 and c.dtype in (torch.float32, torch.float64) and a.is_contiguous() and b.is_contiguous() and c.is_contiguous()
-    check(lib().hg_block_gemm(ptr(a), ptr(b), ptr(c), i32(1 if c.dtype == torch.float64 else 0), ptr(bg.units), i32(bg.nunits), i32(bg.max_tiles), _stream()), "hg_block_gemm")
+    assert c.dtype in (torch.float32, torch.float64)           # (`void* c`: the one pointer whose type the header leaves to a flag)
+    call("hg_block_gemm", a, b, c, c.dtype == torch.float64, bg.units, bg.nunits, bg.max_tiles)
     return c
 
 
@@ -355,13 +384,11 @@ class Geometry:
         pos = pos.contiguous().float()
         self.edge_index = edge_index.contiguous()
         nbr_shift = nbr_shift.contiguous().float()
-        check(lib().hg_edge_geometry(ptr(pos), ptr(self.edge_index), ptr(nbr_shift), i64(E), f32(cutoff), i32(num_radial), i32(lmax),
-                                     ptr(jtab_dev), ptr(self.rbf), ptr(self.wig), ptr(self.length), ptr(ang), _stream()), "hg_edge_geometry")
+        call("hg_edge_geometry", pos, self.edge_index, nbr_shift, E, cutoff, num_radial, lmax, jtab_dev, self.rbf, self.wig, self.length, ang)
         if rbf_func == "gaussian":                             # GaussianSmearing(0, cutoff, num_radial) x cosine cutoff, from the lengths
             offs = _gaussian_offsets(float(cutoff), int(num_radial), dev)
             delta = float((offs[2][1] - offs[2][0]).item())    # the reference's width: spacing of its fp32 linspace (host copy, no sync)
-            check(lib().hg_radial_basis(ptr(self.length), i64(E), i32(1), f32(cutoff), ptr(offs[1]), f32(delta), i32(num_radial), ptr(self.rbf),
-                                        _stream()), "hg_radial_basis")
+            call("hg_radial_basis", self.length, E, 1, cutoff, offs[1], delta, num_radial, self.rbf)
         elif rbf_func != "bessel":
             raise ValueError(f"Unsupported radial basis function on the MI355X path: {rbf_func}")
         self.src = self.edge_index[0].contiguous()
@@ -389,15 +416,14 @@ def radial_hidden(rbf: torch.Tensor, layers: Sequence[torch.Tensor], act_cst: fl
     dims = [int(layers[0].shape[0])] + [int(w.shape[1]) for w in layers]
     W = torch.cat([w.reshape(-1) for w in layers]).contiguous()
     out = torch.empty(E, dims[-1], device=rbf.device, dtype=torch.float32)
-    darr = (C.c_int * len(dims))(*dims)
-    check(lib().hg_radial_hidden(ptr(rbf), i64(E), ptr(W), darr, i32(len(layers)), f32(act_cst), ptr(out), _stream()), "hg_radial_hidden")
+    call("hg_radial_hidden", rbf, E, W, (C.c_int * len(dims))(*dims), len(layers), act_cst, out)
     return out
 
 
 def radial_hidden_cached(geo: "Geometry", layers: Sequence[torch.Tensor], act_cst: float) -> torch.Tensor:
     """radial_hidden(geo.rbf, layers) through the per-forward cache on the geometry object (filled for all weight generators of a
     backbone at once by prefill_radial_hidden; computed singly otherwise)"""
-    cache = geo.__dict__.setdefault("_hcache", {})
+    cache = _hcache(geo)
     key = id(layers[0])
     if key not in cache:
         cache[key] = radial_hidden(geo.rbf, layers, act_cst)
@@ -409,7 +435,7 @@ def prefill_radial_hidden(geo: "Geometry", generators: Sequence[Sequence[torch.T
     H = radial_hidden_multi(geo.rbf, generators, act_cst)
     if H is None:
         return False
-    cache = geo.__dict__.setdefault("_hcache", {})
+    cache = _hcache(geo)
     for m, g in enumerate(generators):
         cache[id(g[0])] = H[m]
     return True
@@ -430,16 +456,13 @@ class KanGenerator:
 @_on_tensor_device
 def kan_hidden_multi(rbf: torch.Tensor, generators: Sequence[KanGenerator]) -> torch.Tensor:
     """Phi [n, E, width] of SEVERAL KAN weight generators of one shape that read the same basis rows, one launch (hg_kan_hidden)"""
-    _require_gpu(rbf)
     g0 = generators[0]
     assert all(g.shape_key == g0.shape_key for g in generators), "use_kan: generators of one launch share their layer widths and grid size"
-    assert rbf.dtype == torch.float32 and rbf.is_contiguous() and rbf.shape[1] == g0.dims[0]
+    assert rbf.shape[1] == g0.dims[0]
     E = rbf.shape[0]
     blob = g0.blob if len(generators) == 1 else torch.cat([g.blob for g in generators])
     out = torch.empty(len(generators), E, g0.width, device=rbf.device, dtype=torch.float32)        # the kernel writes every column, padding included
-    darr = (C.c_int * len(g0.dims))(*g0.dims)
-    check(lib().hg_kan_hidden(ptr(rbf), i64(E), ptr(blob), i64(g0.blob.numel()), i32(len(generators)), darr, i32(len(g0.dims) - 1), i32(g0.grid_size),
-                              i32(1 if g0.packed else 0), ptr(out), _stream()), "hg_kan_hidden")
+    call("hg_kan_hidden", rbf, E, blob, g0.blob.numel(), len(generators), (C.c_int * len(g0.dims))(*g0.dims), len(g0.dims) - 1, g0.grid_size, bool(g0.packed), out)
     return out
 
 
@@ -450,7 +473,7 @@ def kan_hidden(rbf: torch.Tensor, gen: KanGenerator) -> torch.Tensor:
 
 def kan_hidden_cached(geo: "Geometry", gen: KanGenerator) -> torch.Tensor:
     """kan_hidden(geo.rbf, gen) through the per-forward cache on the geometry object (radial_hidden_cached's; filled by prefill_kan_hidden)"""
-    cache = geo.__dict__.setdefault("_hcache", {})
+    cache = _hcache(geo)
     key = id(gen)
     if key not in cache:
         cache[key] = kan_hidden(geo.rbf, gen)
@@ -462,7 +485,7 @@ def prefill_kan_hidden(geo: "Geometry", generators: Sequence[KanGenerator]) -> b
     groups: dict = {}
     for g in generators:
         groups.setdefault(g.shape_key, []).append(g)
-    cache = geo.__dict__.setdefault("_hcache", {})
+    cache = _hcache(geo)
     for gens in groups.values():
         Phi = kan_hidden_multi(geo.rbf, gens)
         for m, g in enumerate(gens):
@@ -478,7 +501,7 @@ def mfma_probe(device, iters: int = 4000, reps: int = 3) -> float:
         src = torch.randn(65536, device=dev)
         nblocks = 2 * torch.cuda.get_device_properties(dev).multi_processor_count
         out = torch.empty(nblocks * 256, device=dev)
-        run = lambda: check(lib().hg_mfma_probe(ptr(src), ptr(out), i32(nblocks), i32(iters), _stream()), "hg_mfma_probe")
+        run = lambda: call("hg_mfma_probe", src, out, nblocks, iters)
         run()
         torch.cuda.synchronize(dev)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -502,7 +525,7 @@ def radial_hidden_multi(rbf: torch.Tensor, generators: Sequence[Sequence[torch.T
     E = rbf.shape[0]
     W = torch.cat([w.reshape(-1) for g in generators for w in g]).contiguous()
     out = torch.empty(len(generators), E, 64, device=rbf.device, dtype=torch.float32)
-    check(lib().hg_radial_hidden_multi(ptr(rbf), i64(E), ptr(W), i32(len(generators)), f32(act_cst), ptr(out), _stream()), "hg_radial_hidden_multi")
+    call("hg_radial_hidden_multi", rbf, E, W, len(generators), act_cst, out)
     return out
 
 
@@ -516,13 +539,8 @@ def rotate_gather(x: torch.Tensor, idx: Optional[torch.Tensor], geo: Geometry, c
     out2 = torch.empty(E, Dp, device=x.device, dtype=torch.float32) if x2 is not None else None
     if x2 is not None:
         assert x2.stride(0) == x.stride(0)
-    check(lib().hg_rotate_gather(ptr(x), ptr(x2), i64(x.stride(0)), ptr(idx), ptr(idx2), ptr(geo.wig), i32(geo.nW), geo.wig_off,
-                                 ptr(chan_tab), i32(chan_tab.shape[0]), i64(E), i32(1 if transpose else 0), ptr(out), ptr(out2), i64(Dp),
-                                 _stream()), "hg_rotate_gather")
+    call("hg_rotate_gather", x, x2, x.stride(0), idx, idx2, geo.wig, geo.nW, geo.wig_off, chan_tab, chan_tab.shape[0], E, bool(transpose), out, out2, Dp)
     return out if x2 is None else (out, out2)
-
-
-PROFILE_EVENTS = None        # bench.py sets this to a list: (start, end, rows, tag) HIP event pairs around hg_tp_fused launches
 
 
 @_on_tensor_device
@@ -534,47 +552,26 @@ def tp_fused(dp: DeviceProgram, srcs: List[torch.Tensor], rows: int, h2n=None, h
     res: up to two residual row tensors in the output's planar layout, added in the epilogue (segment-stationary programs).
     reduce = (eperm, run_id, R) of topo.Topology.receiver_major(): the launch walks the rows in the order eperm and writes the R run sums
     instead of one row per edge (the fused node scatter; input-stationary single-part launches only)."""
-    _require_gpu(srcs[0])
     assert (gather is None and rot_mask == 0) or dp.sched is not None
     res = [r for r in res if r is not None]
-    assert len(res) <= 2 and (not res or dp.sched is None)
-    for r in res:
-        assert r.shape == (rows, dp.out_dim) and r.stride(1) == 1
+    assert len(res) <= 2 and (not res or dp.sched is None) and all(r.shape == (rows, dp.out_dim) for r in res)
     parts = dp.is_parts_for(rows) if dp.sched is not None else 1       # decided ONCE per launch (it reads the environment): the allocation, the tables and the weights agree
     assert reduce is None or (dp.sched is not None and parts == 1)
     alloc = torch.zeros if isinstance(parts, tuple) else torch.empty  # (the 2d split ADDS its tiles into zero-filled rows: plan.is_schedule ("2d", P, K))
     out = alloc(rows if reduce is None else reduce[2], dp.out_dim, device=srcs[0].device, dtype=torch.float32)      # the kernel writes every slot incl. zero channel padding
-    n = len(srcs)
-    sp = (C.c_void_p * 4)(*([s.data_ptr() for s in srcs] + [0] * (4 - n)))
-    ss = (C.c_int64 * 4)(*([int(s.stride(0)) for s in srcs] + [0] * (4 - n)))
-    wig, nW, woff = (ptr(geo.wig), geo.nW, geo.wig_off) if geo is not None else (C.c_void_p(0), 0, (C.c_int * 8)())
-    if PROFILE_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()                                   # torch's current stream == the launch stream (see _stream())
-    if dp.sched is not None:
-        check_build_config()
-        check_w3_split()
-        sc, (t_segs, t_blocks, t_phases, t_groups, t_items, t_parts, t_rowtab) = dp.is_tables(parts)
-        gl = list(gather) + [None] * (4 - len(gather)) if gather is not None else [None] * 4
-        gp = (C.c_void_p * 4)(*[(t.data_ptr() if t is not None else 0) for t in gl])
-        check(lib().hg_tp_is(sp, ss, i32(n), ptr(h2n), ptr(h2e), i32(dp.hidden), wig, i32(nW), woff, ptr(dp.is_weights(parts)), ptr(t_segs),
-                             ptr(t_blocks), ptr(t_phases), ptr(t_groups), ptr(t_items), ptr(t_parts),
-                             np.ascontiguousarray(dp.part_table_host(sc)).ctypes.data_as(C.c_void_p), i32(sc.part_table.shape[0]), ptr(t_rowtab),
-                             i32(sc.lds_floats * 4), gp, i32(rot_mask), ptr(reduce[0]) if reduce is not None else C.c_void_p(0),
-                             ptr(reduce[1]) if reduce is not None else C.c_void_p(0), ptr(out), i64(dp.out_dim), i64(rows), _stream()), "hg_tp_is")
-    else:
-        check(lib().hg_tp_fused(sp, ss, i32(n), ptr(h2n), ptr(h2e), i32(dp.hidden), wig, i32(nW), woff, ptr(dp.weights), ptr(dp.segs),
-                                i32(dp.nseg), ptr(dp.items), ptr(out), i64(dp.out_dim), i64(rows), i32(dp.lds_bytes), i32(dp.flags),
-                                C.c_void_p(res[0].data_ptr() if res else 0), i64(res[0].stride(0) if res else 0),
-                                C.c_void_p(res[1].data_ptr() if len(res) > 1 else 0), i64(res[1].stride(0) if len(res) > 1 else 0), _stream()),
-              "hg_tp_fused")
-    if PROFILE_EVENTS is not None:
-        ev1.record()
-        PROFILE_EVENTS.append((ev0, ev1, rows, tag))
+    head = (*_row_slots(srcs), len(srcs), h2n, h2e, dp.hidden, *_wigner(geo))          # (both entry points begin alike)
+    with _profiled(rows, tag):
+        if dp.sched is not None:
+            check_build_config()
+            check_w3_split()
+            sc, tables = dp.is_tables(parts)
+            eperm, run_id = reduce[:2] if reduce is not None else (None, None)
+            call("hg_tp_is", *head, dp.is_weights(parts), *tables[:6], np.ascontiguousarray(dp.part_table_host(sc)), sc.part_table.shape[0], tables[6],
+                 sc.lds_floats * 4, _row_slots(gather or ())[0], rot_mask, eperm, run_id, out, dp.out_dim, rows)
+        else:
+            call("hg_tp_fused", *head, dp.weights, dp.segs, dp.nseg, dp.items, out, dp.out_dim, rows, dp.lds_bytes, dp.flags, *_residuals(res))
     return out
 
-
-import collections
 
 _SCATTER_CACHE: "collections.OrderedDict" = collections.OrderedDict()     # LRU over (sort order, counts) of index tensors, bounded in entries AND bytes
 _SCATTER_CACHE_MAX_ENTRIES = 64
@@ -631,25 +628,15 @@ class DeviceRowProgram:
 @_on_tensor_device
 def row_program(drp: DeviceRowProgram, x: torch.Tensor, res: Sequence[torch.Tensor] = (), row_idx: Optional[torch.Tensor] = None, tag: str = "row_program") -> torch.Tensor:
     """run a plan.RowProgram on planar rows x [rows, din] (rows gathered by row_idx when given) -> [rows, dout] (+ the rows in `res`)"""
-    _require_gpu(x)
     rp = drp.rp
     x = x if x.stride(1) == 1 else x.contiguous()
     rows = int(row_idx.shape[0]) if row_idx is not None else int(x.shape[0])
     assert x.shape[1] >= rp.din and len(res) <= 2
     y = torch.empty(rows, rp.dout, device=x.device, dtype=torch.float32)
     r = [t if t.stride(1) == 1 else t.contiguous() for t in res]
-    rp_ = lambda i: C.c_void_p(r[i].data_ptr() if i < len(r) else 0)
-    rs_ = lambda i: i64(r[i].stride(0) if i < len(r) else 0)
-    if PROFILE_EVENTS is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().hg_row_program(ptr(x), i64(x.stride(0)), C.c_void_p(row_idx.data_ptr() if row_idx is not None else 0), i32(rp.din), ptr(y), i64(y.stride(0)),
-                               i32(rp.dout), rp_(0), rs_(0), rp_(1), rs_(1), ptr(drp.stages), i32(int(rp.stages.shape[0])), ptr(drp.units), ptr(drp.weights),
-                               ptr(drp.act_tab), ptr(drp.out_tab), i32(int(rp.act_tab.shape[0])), i32(int(rp.out_tab.shape[0])), drp.consts, i32(rp.in_buf), i32(rp.out_buf), i32(rp.rs[0]), i32(rp.rs[1]), i32(rp.strip),
-                               i64(rows), _stream()), "hg_row_program")
-    if PROFILE_EVENTS is not None:
-        ev1.record()
-        PROFILE_EVENTS.append((ev0, ev1, rows, tag))
+    with _profiled(rows, tag):
+        call("hg_row_program", x, x.stride(0), row_idx, rp.din, y, y.stride(0), rp.dout, *_residuals(r), drp.stages, rp.stages.shape[0], drp.units,
+             drp.weights, drp.act_tab, drp.out_tab, rp.act_tab.shape[0], rp.out_tab.shape[0], drp.consts, rp.in_buf, rp.out_buf, rp.rs[0], rp.rs[1], rp.strip, rows)
     return y
 
 
@@ -675,29 +662,24 @@ def tp_wgrad(dwf: DeviceWgFused, srcs: Sequence[Optional[torch.Tensor]], g: torc
              nsplit: Optional[int] = None):
     """one launch of the fused weight-gradient kernel over all rows of `g`: (acc [nsplit, acc_floats], [gs per branch [rows, n_channels]]).
     srcs: edge-frame planar source rows by slot (None for slots the block does not use)."""
-    _require_gpu(g)
+    _require_gpu(g)                # (g.device is made current below)
     wf = dwf.wf
     rows = int(g.shape[0])
     S = int(nsplit or dwf.nsplit_for(rows))
     acc = torch.zeros(S, wf.acc_floats, device=g.device, dtype=torch.float32)
     alloc = torch.empty if wf.gs_complete else torch.zeros      # (every channel of every row is written by exactly one wave when the row tiles cover all channels)
     gs = [alloc(rows, n, device=g.device, dtype=torch.float32) for n in wf.nch]
-    n = len(srcs)
     keep = [(t if t.stride(1) == 1 else t.contiguous()) if t is not None else None for t in srcs]      # (column windows of wider rows pass as they are: pointer + row stride)
     for t in keep:
-        assert t is None or (t.dtype == torch.float32 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0), "hg_tp_wgrad stages float4 pieces of fp32 rows"
-    sp = (C.c_void_p * 4)(*([(t.data_ptr() if t is not None else 0) for t in keep] + [0] * (4 - n)))
-    ss = (C.c_int64 * 4)(*([(t.stride(0) if t is not None else 0) for t in keep] + [0] * (4 - n)))
+        assert t is None or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0), "hg_tp_wgrad stages float4 pieces of fp32 rows"
     g = g.contiguous()
     h_node = h_node.contiguous()
     h_edge = h_edge.contiguous() if h_edge is not None else None
     assert h_node.shape[1] >= wf.hidden and (h_edge is None or h_edge.stride(0) == h_node.stride(0))
+    gs1 = gs[1] if len(gs) > 1 else None
     with torch.cuda.device(g.device):
-        check(lib().hg_tp_wgrad(sp, ss, i32(n), ptr(g), i64(g.stride(0)), ptr(h_node), C.c_void_p(h_edge.data_ptr() if h_edge is not None else 0),
-                                i64(h_node.stride(0)), i32(wf.hidden), ptr(gs[0]), i64(gs[0].stride(0)),
-                                C.c_void_p(gs[1].data_ptr() if len(gs) > 1 else 0), i64(gs[1].stride(0) if len(gs) > 1 else 0),
-                                ptr(acc), i64(wf.acc_floats), i32(S), ptr(dwf.units), i32(int(dwf.units.shape[0])), ptr(dwf.weights), ptr(dwf.chtab),
-                                i32(wf.lds_bytes), i64(rows), _stream()), "hg_tp_wgrad")
+        call("hg_tp_wgrad", *_row_slots(keep), len(srcs), g, g.stride(0), h_node, h_edge, h_node.stride(0), wf.hidden, gs[0], gs[0].stride(0),
+             gs1, gs1.stride(0) if gs1 is not None else 0, acc, wf.acc_floats, S, dwf.units, dwf.units.shape[0], dwf.weights, dwf.chtab, wf.lds_bytes, rows)
     return acc, gs
 
 
@@ -705,7 +687,7 @@ def tp_wgrad(dwf: DeviceWgFused, srcs: Sequence[Optional[torch.Tensor]], g: torc
 def segment_sum(msg: torch.Tensor, rowptr: torch.Tensor, perm: torch.Tensor, N: int) -> torch.Tensor:
     Dp = msg.shape[1]
     out = torch.empty(N, Dp, device=msg.device, dtype=torch.float32)
-    check(lib().hg_segment_sum(ptr(msg), i64(msg.stride(0)), ptr(rowptr), ptr(perm), i64(N), i32(Dp), ptr(out), i64(Dp), _stream()), "hg_segment_sum")
+    call("hg_segment_sum", strided(msg), msg.stride(0), rowptr, perm, N, Dp, out, Dp)
     return out
 
 
@@ -715,13 +697,11 @@ def attention_aggregate(K: torch.Tensor, V: torch.Tensor, geo: "Geometry", rowpt
     """AttentionAggregation of the reference (hamgnn/nn/attention.py:126-164) with key = K[sender], query = K[receiver] and the soft
     cutoff weight: [N, Dp] planar node rows from [E, Dp] planar value rows."""
     N, Dp, E = int(K.shape[0]), int(K.shape[1]), geo.E
-    assert V.shape == (E, Dp) and V.stride(1) == 1 and K.stride(1) == 1
+    assert V.shape == (E, Dp)
     logits = torch.empty(E, H, device=K.device, dtype=torch.float32)
-    check(lib().hg_attn_logits(ptr(K), i64(K.stride(0)), ptr(geo.src), ptr(geo.dst), ptr(geo.length), ptr(head_tab), i32(Dp), i32(H),
-                               ptr(cut_param), f32(cutoff), f32(1.0 / math.sqrt(head_dim)), i64(E), ptr(logits), _stream()), "hg_attn_logits")
+    call("hg_attn_logits", strided(K), K.stride(0), geo.src, geo.dst, geo.length, head_tab, Dp, H, cut_param, cutoff, 1.0 / math.sqrt(head_dim), E, logits)
     out = torch.empty(N, Dp, device=K.device, dtype=torch.float32)
-    check(lib().hg_attn_aggregate(ptr(logits), i32(H), ptr(V), i64(V.stride(0)), ptr(rowptr), ptr(perm), ptr(head_tab), i64(N), i32(Dp),
-                                  ptr(out), i64(Dp), _stream()), "hg_attn_aggregate")
+    call("hg_attn_aggregate", logits, H, strided(V), V.stride(0), rowptr, perm, head_tab, N, Dp, out, Dp)
     return out
 
 
@@ -731,8 +711,7 @@ def attention_logits(K: torch.Tensor, geo: "Geometry", head_tab: torch.Tensor, H
     own by the edge-sharded attention, which needs the per-node soft-max statistics of the rank's edges)"""
     Dp, E = int(K.shape[1]), geo.E
     logits = torch.empty(E, H, device=K.device, dtype=torch.float32)
-    check(lib().hg_attn_logits(ptr(K), i64(K.stride(0)), ptr(geo.src), ptr(geo.dst), ptr(geo.length), ptr(head_tab), i32(Dp), i32(H),
-                               ptr(cut_param), f32(cutoff), f32(1.0 / math.sqrt(head_dim)), i64(E), ptr(logits), _stream()), "hg_attn_logits")
+    call("hg_attn_logits", strided(K), K.stride(0), geo.src, geo.dst, geo.length, head_tab, Dp, H, cut_param, cutoff, 1.0 / math.sqrt(head_dim), E, logits)
     return logits
 
 
@@ -742,8 +721,7 @@ def gate(x: torch.Tensor, tabs, consts: torch.Tensor) -> torch.Tensor:
     act_tab, out_tab = tabs
     rows, Dout = x.shape[0], int(out_tab.shape[0])
     out = torch.empty(rows, Dout, device=x.device, dtype=torch.float32)
-    check(lib().hg_gate(ptr(x), i64(x.stride(0)), ptr(act_tab), i32(act_tab.shape[0]), ptr(out_tab), i32(Dout), ptr(consts), i64(rows), ptr(out),
-                        i64(Dout), _stream()), "hg_gate")
+    call("hg_gate", strided(x), x.stride(0), act_tab, act_tab.shape[0], out_tab, Dout, consts, rows, out, Dout)
     return out
 
 
@@ -752,31 +730,26 @@ NORM_ACT_EPS = 1e-8          # epsilon of the reference's NormActivation (intera
 
 def norm_act(x: torch.Tensor, chan_tab: torch.Tensor) -> torch.Tensor:
     """e3nn NormActivation (ssp, normalize, eps 1e-8) on planar rows; chan_tab = plan.norm_act_table(irreps) on the device"""
-    _require_gpu(x)
-    assert x.dtype == torch.float32 and x.stride(1) == 1
     rows, D = x.shape
     out = torch.empty(rows, D, device=x.device, dtype=torch.float32)
-    check(lib().hg_norm_act(ptr(x), i64(x.stride(0)), ptr(chan_tab), i32(chan_tab.shape[0]), f32(NORM_ACT_EPS), i64(rows), ptr(out), i64(D), i32(D), _stream()),
-          "hg_norm_act")
+    call("hg_norm_act", strided(x), x.stride(0), chan_tab, chan_tab.shape[0], NORM_ACT_EPS, rows, out, D, D)
     return out
 
 
 def norm_act_backward(x: torch.Tensor, gy: torch.Tensor, chan_tab: torch.Tensor) -> torch.Tensor:
-    _require_gpu(x)
-    assert x.dtype == torch.float32 and gy.dtype == torch.float32 and x.stride(1) == 1 and gy.stride(1) == 1 and gy.shape == x.shape
+    assert gy.shape == x.shape
     rows, D = x.shape
     gx = torch.empty(rows, D, device=x.device, dtype=torch.float32)
-    check(lib().hg_norm_act_backward(ptr(x), i64(x.stride(0)), ptr(gy), i64(gy.stride(0)), ptr(chan_tab), i32(chan_tab.shape[0]), f32(NORM_ACT_EPS), i64(rows),
-                                     ptr(gx), i64(D), i32(D), _stream()), "hg_norm_act_backward")
+    call("hg_norm_act_backward", strided(x), x.stride(0), strided(gy), gy.stride(0), chan_tab, chan_tab.shape[0], NORM_ACT_EPS, rows, gx, D, D)
     return gx
 
 
 @_on_tensor_device
 def add_rows(a, b, c=None):
+    """a + b (+ c) on [rows, D] rows; column windows of wider rows pass as they are (pointer and row stride), the sum comes back contiguous"""
     rows, D = a.shape
-    out = torch.empty_like(a)
-    check(lib().hg_add_rows(ptr(a), i64(a.stride(0)), ptr(b), i64(b.stride(0)), ptr(c), i64(c.stride(0) if c is not None else 0), i64(rows),
-                            i32(D), ptr(out), i64(D), _stream()), "hg_add_rows")
+    out = torch.empty(rows, D, device=a.device, dtype=a.dtype)
+    call("hg_add_rows", strided(a), a.stride(0), strided(b), b.stride(0), strided(c), c.stride(0) if c is not None else 0, rows, D, out, D)
     return out
 
 
@@ -784,7 +757,7 @@ def add_rows(a, b, c=None):
 def to_planar(x: torch.Tensor, imap: torch.Tensor, Dp: int) -> torch.Tensor:
     x = x.contiguous().float()
     out = torch.empty(x.shape[0], Dp, device=x.device, dtype=torch.float32)
-    check(lib().hg_to_planar(ptr(x), i64(x.shape[0]), i32(x.shape[1]), ptr(imap), ptr(out), i32(Dp), _stream()), "hg_to_planar")
+    call("hg_to_planar", x, x.shape[0], x.shape[1], imap, out, Dp)
     return out
 
 
@@ -792,14 +765,14 @@ def to_planar(x: torch.Tensor, imap: torch.Tensor, Dp: int) -> torch.Tensor:
 def from_planar(xp: torch.Tensor, imap: torch.Tensor) -> torch.Tensor:
     D = int(imap.shape[0])
     out = torch.empty(xp.shape[0], D, device=xp.device, dtype=torch.float32)
-    check(lib().hg_from_planar(ptr(xp), i64(xp.shape[0]), i32(xp.shape[1]), ptr(imap), ptr(out), i32(D), _stream()), "hg_from_planar")
+    call("hg_from_planar", xp, xp.shape[0], xp.shape[1], imap, out, D)
     return out
 
 
 @_on_tensor_device
 def embed_lookup(Ta, Tb, z, idx_a, idx_b, rows, T, Tp):
     out = torch.empty(rows, Tp, device=Ta.device, dtype=torch.float32)
-    check(lib().hg_embed_lookup(ptr(Ta), ptr(Tb), ptr(z), ptr(idx_a), ptr(idx_b), i64(rows), i32(T), i32(Tp), ptr(out), _stream()), "hg_embed_lookup")
+    call("hg_embed_lookup", Ta, Tb, z, idx_a, idx_b, rows, T, Tp, out)
     return out
 
 
@@ -808,10 +781,9 @@ def gate_backward(x: torch.Tensor, gy: torch.Tensor, tabs, consts: torch.Tensor)
     """data gradient of gate(x, tabs, consts): [rows, Din] from the gate input rows and the gradient of the gate output rows"""
     act_tab, out_tab = tabs
     rows, Din, Dout = x.shape[0], int(x.shape[1]), int(out_tab.shape[0])
-    assert gy.shape == (rows, Dout) and x.stride(1) == 1 and gy.stride(1) == 1
+    assert gy.shape == (rows, Dout)
     gx = torch.empty(rows, Din, device=x.device, dtype=torch.float32)
-    check(lib().hg_gate_backward(ptr(x), i64(x.stride(0)), ptr(gy), i64(gy.stride(0)), ptr(act_tab), i32(act_tab.shape[0]), ptr(out_tab), i32(Dout),
-                                 ptr(consts), i64(rows), i32(Din), ptr(gx), i64(Din), _stream()), "hg_gate_backward")
+    call("hg_gate_backward", strided(x), x.stride(0), strided(gy), gy.stride(0), act_tab, act_tab.shape[0], out_tab, Dout, consts, rows, Din, gx, Din)
     return gx
 
 
@@ -819,9 +791,7 @@ def gate_backward(x: torch.Tensor, gy: torch.Tensor, tabs, consts: torch.Tensor)
 def ham_merge(coeff, geo: Optional[Geometry], slot_tab, cg_ptr, cg_idx, cg_val, nout):
     rows = coeff.shape[0]
     out = torch.empty(rows, nout, device=coeff.device, dtype=torch.float32)
-    wig, nW, woff = (ptr(geo.wig), geo.nW, geo.wig_off) if geo is not None else (C.c_void_p(0), 0, (C.c_int * 8)())
-    check(lib().hg_ham_merge(ptr(coeff), i64(coeff.stride(0)), wig, i32(nW), woff, ptr(slot_tab), i32(slot_tab.shape[0]), ptr(cg_ptr),
-                             ptr(cg_idx), ptr(cg_val), i32(nout), i64(rows), ptr(out), _stream()), "hg_ham_merge")
+    call("hg_ham_merge", strided(coeff), coeff.stride(0), *_wigner(geo), slot_tab, slot_tab.shape[0], cg_ptr, cg_idx, cg_val, nout, rows, out)
     return out
 
 
@@ -830,15 +800,11 @@ def ham_finish(Hraw, inv, H0, orb_mask, z, idx_a, idx_b, nao, sign=1.0, symmetri
     """Hraw: [rows, >= nao^2] (a column slice of a wider buffer is fine: the row stride is passed on).
     out: optional contiguous [rows, nao^2] destination (e.g. the row range of the [N+E, nao^2] result: no torch.cat afterwards)."""
     rows = Hraw.shape[0]
-    assert Hraw.stride(1) == 1
     if out is None:
         out = torch.empty(rows, nao * nao, device=Hraw.device, dtype=torch.float32)
-    assert out.shape == (rows, nao * nao) and out.is_contiguous() and out.dtype == torch.float32
+    assert out.shape == (rows, nao * nao)
     mask_w = int(orb_mask.shape[1]) if orb_mask is not None else 0
-    _require_gpu(Hraw)
-    check(lib().hg_ham_finish(C.c_void_p(Hraw.data_ptr()), i64(Hraw.stride(0)), ptr(inv), ptr(H0), ptr(orb_mask), i32(mask_w), ptr(z), ptr(idx_a), ptr(idx_b),
-                              i32(nao), f32(sign), i32((1 if symmetrize else 0) | (2 if h0_after_mask else 0)), i64(rows), ptr(out),
-                              _stream()), "hg_ham_finish")
+    call("hg_ham_finish", strided(Hraw), Hraw.stride(0), inv, H0, orb_mask, mask_w, z, idx_a, idx_b, nao, sign, bool(symmetrize) | 2 * bool(h0_after_mask), rows, out)
     return out
 
 
@@ -847,17 +813,13 @@ def ham_readout(coeff, geo: Optional[Geometry], slot_tab, cg_ptr, cg_idx, cg_val
                 lmax_ham, sign=1.0, symmetrize=True, h0_after_mask=False):
     """one-pass non-SOC read-out of `coeff` rows into `out` [rows, nao^2]; pairs = (pair_a, pair_b) int64 row indices or None (rows pair
     with themselves: on-site)."""
-    _require_gpu(coeff)
     rows = coeff.shape[0]
-    assert out.shape == (rows, nao * nao) and out.is_contiguous() and out.dtype == torch.float32
-    wig, nW, woff = (ptr(geo.wig), geo.nW, geo.wig_off) if geo is not None else (C.c_void_p(0), 0, (C.c_int * 8)())
+    assert out.shape == (rows, nao * nao)
     pa, pb = pairs if pairs is not None else (None, None)
     npairs = rows if pa is None else pa.shape[0]
     mask_w = int(orb_mask.shape[1]) if orb_mask is not None else 0
-    check(lib().hg_ham_readout(ptr(coeff), i64(coeff.stride(0)), i32(coeff.shape[1]), wig, i32(nW), woff, i32(lmax_ham), ptr(slot_tab), i32(slot_tab.shape[0]), ptr(cg_ptr),
-                               ptr(cg_idx), ptr(cg_val), i32(cg_idx.shape[0]), i32(nao), ptr(pa), ptr(pb), i64(npairs), ptr(H0), ptr(orb_mask),
-                               i32(mask_w), ptr(z), ptr(idx_a), ptr(idx_b), f32(sign), i32((1 if symmetrize else 0) | (2 if h0_after_mask else 0)),
-                               C.c_void_p(out.data_ptr()), _stream()), "hg_ham_readout")
+    call("hg_ham_readout", strided(coeff), coeff.stride(0), coeff.shape[1], *_wigner(geo), lmax_ham, slot_tab, slot_tab.shape[0], cg_ptr, cg_idx, cg_val, cg_idx.shape[0], nao,
+         pa, pb, npairs, H0, orb_mask, mask_w, z, idx_a, idx_b, sign, bool(symmetrize) | 2 * bool(h0_after_mask), out)
     return out
 
 
@@ -865,7 +827,7 @@ def ham_readout(coeff, geo: Optional[Geometry], slot_tab, cg_ptr, cg_idx, cg_val
 def block_mean(x, tab, nao):
     rows = x.shape[0]
     out = torch.empty(rows, nao * nao, device=x.device, dtype=torch.float32)
-    check(lib().hg_block_mean(ptr(x), i64(x.stride(0)), ptr(tab), i32(nao), i64(rows), ptr(out), _stream()), "hg_block_mean")
+    call("hg_block_mean", strided(x), x.stride(0), tab, nao, rows, out)
     return out
 
 
@@ -874,20 +836,16 @@ def soc_assemble(H, ksi, L, inv, H0r, H0i, nao, symmetrize=True, zero_diag=False
     rows = H.shape[0]
     outr = torch.empty(rows, 4 * nao * nao, device=H.device, dtype=torch.float32)
     outi = torch.empty_like(outr)
-    check(lib().hg_soc_assemble(ptr(H), ptr(ksi), ptr(L), ptr(inv), ptr(H0r), ptr(H0i), i32(nao), i32(1 if symmetrize else 0),
-                                i32(1 if zero_diag else 0), i64(rows), ptr(outr), ptr(outi), _stream()), "hg_soc_assemble")
+    call("hg_soc_assemble", H, ksi, L, inv, H0r, H0i, nao, bool(symmetrize), bool(zero_diag), rows, outr, outi)
     return outr, outi
 
 
 @_on_tensor_device
 def hk_assemble(on, off, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_atoms, nao, orank, ooff, M):
     """[nk, M, M] complex64 k-space matrix of one crystal in the compact orbital basis (see include/hamgnn_hip.h:hg_hk_assemble)"""
-    _require_gpu(on)
     nk = int(kvec.shape[0])
     out = torch.zeros(nk, M, M, 2, device=on.device, dtype=torch.float32)
-    check(lib().hg_hk_assemble(ptr(on), ptr(off), ptr(nbr_shift), ptr(kvec), i32(nk), ptr(pair_ptr), ptr(pair_edges), ptr(pair_ij),
-                               i64(pair_ij.shape[0]), i32(n_atoms), i32(nao), ptr(orank.to(torch.int32).contiguous()), ptr(ooff), i32(M), ptr(out),
-                               _stream()), "hg_hk_assemble")
+    call("hg_hk_assemble", on, off, nbr_shift, kvec, nk, pair_ptr, pair_edges, pair_ij, pair_ij.shape[0], n_atoms, nao, orank.to(torch.int32).contiguous(), ooff, M, out)
     return torch.view_as_complex(out)
 
 
@@ -904,9 +862,8 @@ def hk_assemble_adjoint(G, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_ato
     Gr = torch.view_as_real(G.contiguous())
     g_on = torch.empty(n_atoms, nao * nao, device=G.device, dtype=torch.float32)
     g_off = torch.empty(n_edges, nao * nao, device=G.device, dtype=torch.float32)
-    check(lib().hg_hk_assemble_adjoint(ptr(Gr), ptr(nbr_shift), ptr(kvec), i32(nk), ptr(pair_ptr), ptr(pair_edges), ptr(pair_ij), i64(pair_ij.shape[0]),
-                                       i32(n_atoms), i64(n_edges), i32(nao), ptr(orank.to(torch.int32).contiguous()), ptr(ooff), i32(M), ptr(g_on),
-                                       ptr(g_off), _stream()), "hg_hk_assemble_adjoint")
+    call("hg_hk_assemble_adjoint", Gr, nbr_shift, kvec, nk, pair_ptr, pair_edges, pair_ij, pair_ij.shape[0], n_atoms, n_edges, nao,
+         orank.to(torch.int32).contiguous(), ooff, M, g_on, g_off)
     return g_on, g_off
 
 
@@ -914,21 +871,16 @@ def hk_assemble_adjoint(G, nbr_shift, kvec, pair_ptr, pair_edges, pair_ij, n_ato
 def mulliken_weights(C_, SC, perm, gptr, wk, Gp):
     """W [ns, Gp] fp32 from the eigenvector rows C_ and S(k) c rows SC, both [ns, M] complex64: column 0 = wk, column 1 + g = wk * the Mulliken
     weight of orbital group g (perm / gptr int32), pad columns 0 (see include/hamgnn_hip.h:hg_mulliken_weights); every element is written"""
-    _require_gpu(C_)
     ns, M = int(C_.shape[0]), int(C_.shape[1])
     G = int(gptr.shape[0]) - 1
     if C_.dtype != torch.complex64 or SC.dtype != torch.complex64 or tuple(SC.shape) != (ns, M) or tuple(wk.shape) != (ns,):
         raise ValueError(f"mulliken_weights: C and SC must be complex64 [{ns}, {M}] and wk [{ns}], got {C_.dtype} {tuple(C_.shape)}, {SC.dtype} {tuple(SC.shape)}, {tuple(wk.shape)}")
-    if perm.dtype != torch.int32 or gptr.dtype != torch.int32 or wk.dtype != torch.float32:
-        raise ValueError("mulliken_weights: perm and gptr must be int32, wk float32")
-    if not (perm.is_contiguous() and gptr.is_contiguous() and wk.is_contiguous()) or perm.dim() != 1 or gptr.dim() != 1 or G < 0:
-        raise ValueError("mulliken_weights: perm, gptr and wk must be contiguous 1-d tensors, gptr with at least one entry")
+    if perm.dim() != 1 or gptr.dim() != 1 or G < 0:
+        raise ValueError("mulliken_weights: perm and gptr must be 1-d tensors, gptr with at least one entry")
     if Gp < 1 + G:
         raise ValueError(f"mulliken_weights: Gp = {Gp} holds no room for the state weight and {G} groups")
     W = torch.empty(ns, Gp, device=C_.device, dtype=torch.float32)
-    Cr, SCr = torch.view_as_real(C_.contiguous()), torch.view_as_real(SC.contiguous())
-    check(lib().hg_mulliken_weights(ptr(Cr), ptr(SCr), i64(ns), i32(M), ptr(perm), ptr(gptr),
-                                    i32(G), i32(Gp), ptr(wk), ptr(W), _stream()), "hg_mulliken_weights")
+    call("hg_mulliken_weights", torch.view_as_real(C_.contiguous()), torch.view_as_real(SC.contiguous()), ns, M, perm, gptr, G, Gp, wk, W)
     return W
 
 
@@ -936,20 +888,16 @@ def mulliken_weights(C_, SC, perm, gptr, wk, Gp):
 def dos_broaden(eps, W, E0, dE, ne, sigma, D=None, accumulate=False):
     """D [ne, Gp] fp32 (+)= Gaussians of width sigma around the ASCENDING eps [ns], weighted by W [ns, Gp], on the grid E0 + j dE (see
     include/hamgnn_hip.h:hg_dos_broaden).  accumulate adds to the given D; otherwise every element of D is written."""
-    _require_gpu(W)
+    if W.dim() != 2 or tuple(eps.shape) != (W.shape[0],):
+        raise ValueError(f"dos_broaden: W must be [ns, Gp] and eps [ns], got {tuple(W.shape)}, {tuple(eps.shape)}")
     ns, Gp = int(W.shape[0]), int(W.shape[1])
-    if eps.dtype != torch.float32 or W.dtype != torch.float32 or tuple(eps.shape) != (ns,):
-        raise ValueError(f"dos_broaden: eps must be float32 [{ns}] and W float32, got {eps.dtype} {tuple(eps.shape)}, {W.dtype}")
-    if not (eps.is_contiguous() and W.is_contiguous()) or W.dim() != 2 or (D is not None and not D.is_contiguous()):
-        raise ValueError("dos_broaden: eps, W and D must be contiguous (a sliced tensor would be read or written with the wrong stride)")
     if D is None:
         if accumulate:
             raise ValueError("dos_broaden: accumulate needs the D to add to")
         D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
-    elif D.dtype != torch.float32 or tuple(D.shape) != (ne, Gp):
-        raise ValueError(f"dos_broaden: D must be float32 [{ne}, {Gp}], got {D.dtype} {tuple(D.shape)}")
-    check(lib().hg_dos_broaden(ptr(eps), ptr(W), i64(ns), i32(Gp), C.c_double(float(E0)), C.c_double(float(dE)), i32(ne), C.c_double(float(sigma)),
-                               i32(1 if accumulate else 0), ptr(D), _stream()), "hg_dos_broaden")
+    elif tuple(D.shape) != (ne, Gp):
+        raise ValueError(f"dos_broaden: D must be [{ne}, {Gp}], got {tuple(D.shape)}")
+    call("hg_dos_broaden", eps, W, ns, Gp, E0, dE, ne, sigma, bool(accumulate), D)
     return D
 
 
@@ -958,17 +906,13 @@ def dos_tetra(eps, W, tet, kt, band_lo, band_hi, E0, dE, ne, mode=0, D=None, acc
     """D [ne, Gp] fp32 (+)= the linear tetrahedron method's DOS (mode 0) or number of states (mode 1) on the grid E0 + j dE: eps [nk, nb] ascending in b,
     W [nk, nb, Gp], tet int32 [nt, 4], kt = (kt_ptr [nk + 1], kt_tet [4 nt], kt_corner [4 nt]) int32 (dos.corner_table), band_lo / band_hi [nb] = min / max
     of eps over k (see include/hamgnn_hip.h:hg_dos_tetra).  accumulate adds to the given D; otherwise every element of D is written."""
-    _require_gpu(W)
     if W.dim() != 3 or eps.dim() != 2 or tet.dim() != 2 or len(kt) != 3:
         raise ValueError(f"dos_tetra: eps must be [nk, nb], W [nk, nb, Gp], tet [nt, 4] and kt three tensors, got {tuple(eps.shape)}, {tuple(W.shape)}, {tuple(tet.shape)}")
     nk, nb, Gp = (int(v) for v in W.shape)
     nt = int(tet.shape[0])
     kt_ptr, kt_tet, kt_corner = kt
-    f32s, i32s = (eps, W, band_lo, band_hi), (tet, kt_ptr, kt_tet, kt_corner)
-    if any(t.dtype != torch.float32 for t in f32s) or any(t.dtype != torch.int32 for t in i32s):
-        raise ValueError("dos_tetra: eps, W, band_lo and band_hi must be float32, tet and the corner table int32")
-    if not all(t.is_contiguous() for t in f32s + i32s) or (D is not None and not D.is_contiguous()):
-        raise ValueError("dos_tetra: eps, W, tet, the corner table, band_lo, band_hi and D must be contiguous (a sliced tensor would be read or written with the wrong stride)")
+    if any(t.dtype != torch.float32 for t in (eps, W, band_lo, band_hi)) or any(t.dtype != torch.int32 for t in (tet, kt_ptr, kt_tet, kt_corner)):
+        raise ValueError("dos_tetra: eps, W, band_lo and band_hi must be float32, tet and the corner table int32")          # (tests/test_dos_tetra_cpu.py matches these words)
     if (tuple(eps.shape) != (nk, nb) or tuple(tet.shape) != (nt, 4) or tuple(kt_ptr.shape) != (nk + 1,) or tuple(kt_tet.shape) != (4 * nt,)
             or tuple(kt_corner.shape) != (4 * nt,) or tuple(band_lo.shape) != (nb,) or tuple(band_hi.shape) != (nb,)):
         raise ValueError(f"dos_tetra: shapes do not fit nk = {nk}, nb = {nb}, nt = {nt}: eps {tuple(eps.shape)}, tet {tuple(tet.shape)}, kt_ptr {tuple(kt_ptr.shape)}, "
@@ -979,11 +923,9 @@ def dos_tetra(eps, W, tet, kt, band_lo, band_hi, E0, dE, ne, mode=0, D=None, acc
         if accumulate:
             raise ValueError("dos_tetra: accumulate needs the D to add to")
         D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
-    elif D.dtype != torch.float32 or tuple(D.shape) != (ne, Gp):
-        raise ValueError(f"dos_tetra: D must be float32 [{ne}, {Gp}], got {D.dtype} {tuple(D.shape)}")
-    check(lib().hg_dos_tetra(ptr(eps), ptr(W), i32(nk), i32(nb), i32(Gp), ptr(tet), i64(nt), ptr(kt_ptr), ptr(kt_tet), ptr(kt_corner), ptr(band_lo),
-                             ptr(band_hi), C.c_double(float(E0)), C.c_double(float(dE)), i32(ne), i32(mode), i32(1 if accumulate else 0), ptr(D),
-                             _stream()), "hg_dos_tetra")
+    elif tuple(D.shape) != (ne, Gp):
+        raise ValueError(f"dos_tetra: D must be [{ne}, {Gp}], got {tuple(D.shape)}")
+    call("hg_dos_tetra", eps, W, nk, nb, Gp, tet, nt, kt_ptr, kt_tet, kt_corner, band_lo, band_hi, E0, dE, ne, mode, bool(accumulate), D)
     return D
 
 
@@ -993,27 +935,22 @@ def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, ep
     wk, column 1 + g = wk * (sum of Re(phase c_i^+ X_off[e] c_j) over the edges eidx[eptr[g]:eptr[g + 1]] + sum of Re(c_i^+ X_on[i] c_i) over the atoms
     aidx[aptr[g]:aptr[g + 1]]), pad columns 0 (see include/hamgnn_hip.h:hg_bond_weights); every element is written.  kidx int32 [ns] -> rows of kvec
     [nk, 3]; erow / ecol int32 [E], shift [E, 3]; orank int32 [N, nao], ooff int32 [N].  All tables are checked here, on the host, before the launch."""
-    _require_gpu(C_)
+    _require_gpu(C_)               # (the tables are read below, ahead of the launch)
     if C_.dim() != 2 or C_.dtype != torch.complex64:
         raise ValueError(f"bond_weights: C must be complex64 [ns, M], got {C_.dtype} {tuple(C_.shape)}")
-    if not C_.is_contiguous():
-        raise ValueError("bond_weights: C must be contiguous (a sliced tensor would be read with the wrong stride)")
     ns, M = int(C_.shape[0]), int(C_.shape[1])
-    if orank.dim() != 2 or orank.dtype != torch.int32:
-        raise ValueError(f"bond_weights: orank must be int32 [N, nao], got {orank.dtype} {tuple(orank.shape)}")
+    if orank.dim() != 2:
+        raise ValueError(f"bond_weights: orank must be [N, nao], got {tuple(orank.shape)}")
     N, nao = int(orank.shape[0]), int(orank.shape[1])
     E, nk, G = int(X_off.shape[0]), int(kvec.shape[0]), int(eptr.shape[0]) - 1
-    f32s = {"kvec": (kvec, (nk, 3)), "X_on": (X_on, (N, nao * nao)), "X_off": (X_off, (E, nao * nao)), "shift": (shift, (E, 3)), "wk": (wk, (ns,))}
-    i32s = {"kidx": (kidx, (ns,)), "erow": (erow, (E,)), "ecol": (ecol, (E,)), "ooff": (ooff, (N,)), "eptr": (eptr, (G + 1,)), "aptr": (aptr, (G + 1,)),
-            "eidx": (eidx, (int(eidx.numel()),)), "aidx": (aidx, (int(aidx.numel()),)), "orank": (orank, (N, nao))}
-    for dt, group in ((torch.float32, f32s), (torch.int32, i32s)):
-        for name, (t, shape) in group.items():
-            if t.dtype != dt or tuple(t.shape) != shape:
-                raise ValueError(f"bond_weights: {name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"bond_weights: {name} must be contiguous")
-            if t.device != C_.device:
-                raise ValueError(f"bond_weights: {name} is on {t.device}, C on {C_.device}")
+    shapes = {"kvec": (kvec, (nk, 3)), "X_on": (X_on, (N, nao * nao)), "X_off": (X_off, (E, nao * nao)), "shift": (shift, (E, 3)), "wk": (wk, (ns,)), "kidx": (kidx, (ns,)),
+              "erow": (erow, (E,)), "ecol": (ecol, (E,)), "ooff": (ooff, (N,)), "eptr": (eptr, (G + 1,)), "aptr": (aptr, (G + 1,)), "eidx": (eidx, (int(eidx.numel()),)),
+              "aidx": (aidx, (int(aidx.numel()),))}
+    for name, (t, shape) in shapes.items():
+        if tuple(t.shape) != shape:
+            raise ValueError(f"bond_weights: {name} must be {list(shape)}, got {list(t.shape)}")
+        if t.device != C_.device:                              # (the typed call asks for a GPU tensor, not for this GPU)
+            raise ValueError(f"bond_weights: {name} is on {t.device}, C on {C_.device}")
     if G < 0 or Gp < 1 + G:
         raise ValueError(f"bond_weights: Gp = {Gp} holds no room for the state weight and {G} groups")
     if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
@@ -1031,32 +968,26 @@ def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, ep
     if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
         raise ValueError(f"bond_weights: orank / ooff point outside the {M} compact orbitals of C")
     W = torch.empty(ns, Gp, device=C_.device, dtype=torch.float32)
-    check(lib().hg_bond_weights(ptr(torch.view_as_real(C_)), i64(ns), i32(M), ptr(kidx), ptr(kvec), i32(nk), ptr(X_on), ptr(X_off), ptr(erow), ptr(ecol),
-                                ptr(shift), i64(E), i32(N), i32(nao), ptr(orank), ptr(ooff), ptr(eptr), ptr(eidx), ptr(aptr), ptr(aidx), i32(G), i32(Gp),
-                                ptr(wk), ptr(W), _stream()), "hg_bond_weights")
+    call("hg_bond_weights", torch.view_as_real(C_), ns, M, kidx, kvec, nk, X_on, X_off, erow, ecol, shift, E, N, nao, orank, ooff, eptr, eidx, aptr, aidx, G, Gp, wk, W)
     return W
 
 
 @_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""
-    _require_gpu(H)
     rows = S.shape[0]
     nparts = 256
     scratch = torch.empty(2 * nparts, device=H.device, dtype=torch.float64)
     shift = torch.empty(1, device=H.device, dtype=torch.float32)
-    check(lib().hg_zero_point_shift(ptr(H), ptr(Href), ptr(S), i64(rows), i32(nao), i32(1 if soc else 0), f32(threshold), ptr(scratch),
-                                    i32(nparts), ptr(shift), _stream()), "hg_zero_point_shift")
+    call("hg_zero_point_shift", H, Href, S, rows, nao, bool(soc), threshold, scratch, nparts, shift)
     return shift
 
 
 @_on_tensor_device
 def sym_contraction3(h, z, C, tab, W3, out):
     """adds the nu = 3 term of a `correlation: 3` block to the rows `out` that sym_contraction returned (in place; csrc/sym_contraction.hip)"""
-    _require_gpu(h)
-    check(lib().hg_sym_contraction3(ptr(h), i64(h.stride(0)), ptr(z), i64(h.shape[0]), i32(C), i32(tab["num_ell"]), ptr(tab["ell_off"]), i32(tab["nout"]),
-                                    ptr(tab["out_off"]), ptr(tab["ptr3"]), ptr(tab["ent3"]), ptr(W3), i32(W3.shape[1]), ptr(out), i64(out.stride(0)),
-                                    _stream()), "hg_sym_contraction3")
+    call("hg_sym_contraction3", h, h.stride(0), z, h.shape[0], C, tab["num_ell"], tab["ell_off"], tab["nout"], tab["out_off"], tab["ptr3"], tab["ent3"], W3, W3.shape[1],
+         out, out.stride(0))
     return out
 
 
@@ -1064,11 +995,9 @@ def sym_contraction3(h, z, C, tab, W3, out):
 def sym_contraction_nu(nu, h, z, C, tab, W, out):
     """adds the term of order nu (1 ... 4) of the symmetric contraction to the rows `out` (in place; csrc/sym_contraction.hip): the nu = 4 term of a
     `correlation: 4` block onto what sym_contraction / sym_contraction3 wrote, or every term onto zeros (HG_CORR_KERNEL=nu)"""
-    _require_gpu(h)
     h = h.contiguous()
-    check(lib().hg_sym_contraction_nu(i32(nu), ptr(h), i64(h.stride(0)), ptr(z), i64(h.shape[0]), i32(C), i32(tab["num_ell"]), ptr(tab["ell_off"]),
-                                      i32(tab["nout"]), ptr(tab["out_off"]), ptr(tab[f"ptr{nu}"]), ptr(tab[f"ent{nu}"]), ptr(W), i32(W.shape[1]), ptr(out),
-                                      i64(out.stride(0)), _stream()), "hg_sym_contraction_nu")
+    call("hg_sym_contraction_nu", nu, h, h.stride(0), z, h.shape[0], C, tab["num_ell"], tab["ell_off"], tab["nout"], tab["out_off"], tab[f"ptr{nu}"], tab[f"ent{nu}"],
+         W, W.shape[1], out, out.stride(0))
     return out
 
 
@@ -1115,10 +1044,8 @@ def sym_contraction_nu_backward(nu, h, z, C, tab, W, g_out, g_h, per_node=False)
     else:
         run_ptr, nodes, elem, G = _element_runs(z, T, SYM_NU_RUN)
     gW = torch.empty(G, K, C, device=h.device, dtype=torch.float32)
-    check(lib().hg_sym_contraction_nu_backward(i32(nu), ptr(h), i64(h.stride(0)), ptr(g_out), i64(g_out.stride(0)), ptr(z), i64(N), i32(C),
-                                               i32(tab["num_ell"]), ptr(tab["ell_off"]), i32(tab["nout"]), ptr(tab["out_off"]), ptr(tab[f"ptrH{nu}"]),
-                                               ptr(tab[f"entH{nu}"]), ptr(tab[f"ptrW{nu}"]), ptr(tab[f"entW{nu}"]), ptr(W), i32(K), i64(G), ptr(run_ptr),
-                                               ptr(nodes), ptr(g_h), i64(g_h.stride(0)), ptr(gW), _stream()), "hg_sym_contraction_nu_backward")
+    call("hg_sym_contraction_nu_backward", nu, h, h.stride(0), g_out, g_out.stride(0), z, N, C, tab["num_ell"], tab["ell_off"], tab["nout"], tab["out_off"],
+         tab[f"ptrH{nu}"], tab[f"entH{nu}"], tab[f"ptrW{nu}"], tab[f"entW{nu}"], W, K, G, run_ptr, nodes, g_h, g_h.stride(0), gW)
     if per_node:
         return gW
     return scatter_rows(elem, gW.reshape(G, K * C), T, persistent=False).reshape(T, K, C)
@@ -1127,12 +1054,10 @@ def sym_contraction_nu_backward(nu, h, z, C, tab, W, g_out, g_h, per_node=False)
 @_on_tensor_device
 def sym_contraction(h, z, C, tab, W1, W2, out_dim):
     """tab: device tensors of plan.sym_contraction_tables; W1 [nel, K1, C], W2 [nel, K2, C]; returns planar hidden rows [N, out_dim]"""
-    _require_gpu(h)
     N = h.shape[0]
     out = torch.zeros(N, out_dim, device=h.device, dtype=torch.float32)           # channel padding stays zero
-    check(lib().hg_sym_contraction(ptr(h), i64(h.stride(0)), ptr(z), i64(N), i32(C), i32(tab["num_ell"]), ptr(tab["ell_off"]), i32(tab["nout"]),
-                                   ptr(tab["out_off"]), ptr(tab["ptr1"]), ptr(tab["ent1"]), ptr(tab["ptr2"]), ptr(tab["ent2"]), ptr(W1),
-                                   i32(W1.shape[1]), ptr(W2), i32(W2.shape[1]), ptr(out), i64(out_dim), _stream()), "hg_sym_contraction")
+    call("hg_sym_contraction", h, h.stride(0), z, N, C, tab["num_ell"], tab["ell_off"], tab["nout"], tab["out_off"], tab["ptr1"], tab["ent1"], tab["ptr2"], tab["ent2"],
+         W1, W1.shape[1], W2, W2.shape[1], out, out_dim)
     return out
 
 
@@ -1150,17 +1075,13 @@ class CellList:
 def neighbour_bin(pos: torch.Tensor, cell: torch.Tensor, batch, atom_ptr: torch.Tensor, rcut: torch.Tensor, flags: torch.Tensor) -> CellList:
     """hg_neighbour_bin: pos [N, 3] fp32, cell [B, 3, 3] fp32, batch [N] int64 or None (one crystal), atom_ptr [B + 1] int64, rcut: fp64 device scalar (the largest
     r_i + r_j), flags: int32 device error word"""
-    _require_gpu(pos)
     N, B = int(pos.shape[0]), int(cell.shape[0])
-    assert pos.dtype == torch.float32 and cell.dtype == torch.float32 and rcut.dtype == torch.float64 and flags.dtype == torch.int32 and atom_ptr.dtype == torch.int64
-    assert batch is None or (batch.dtype == torch.int64 and batch.shape[0] == N)
-    assert pos.is_contiguous() and cell.is_contiguous() and tuple(cell.shape[1:]) == (3, 3) and atom_ptr.shape[0] == B + 1
+    assert (batch is None or batch.shape[0] == N) and tuple(cell.shape[1:]) == (3, 3) and atom_ptr.shape[0] == B + 1
     dev = pos.device
     bins_cap = N + 27 * B
     cl = CellList(torch.empty(B, 20, device=dev, dtype=torch.float64), torch.empty(B, 8, device=dev, dtype=torch.int32), torch.empty(N, device=dev, dtype=torch.int64),
                   torch.empty(N, 3, device=dev, dtype=torch.int32), bins_cap, B)
-    check(lib().hg_neighbour_bin(ptr(pos), ptr(cell), ptr(batch), ptr(atom_ptr), ptr(rcut), i64(N), i32(B), i64(bins_cap), ptr(cl.cpar), ptr(cl.ipar), ptr(cl.bin_id),
-                                 ptr(cl.wrap), ptr(flags), _stream()), "hg_neighbour_bin")
+    call("hg_neighbour_bin", pos, cell, batch, atom_ptr, rcut, N, B, bins_cap, cl.cpar, cl.ipar, cl.bin_id, cl.wrap, flags)
     return cl
 
 
@@ -1168,32 +1089,28 @@ def neighbour_bin(pos: torch.Tensor, cell: torch.Tensor, batch, atom_ptr: torch.
 def neighbour_pairs(pos: torch.Tensor, radius: torch.Tensor, batch, cl: CellList, flags: torch.Tensor, seg_ptr=None, capacity: int = 0) -> torch.Tensor:
     """hg_neighbour_pairs: seg_ptr None -> the count pass, edges per centre [N] int64; else the fill pass, one packed key per edge [capacity] int64 (centre i's in
     seg_ptr[i] .. seg_ptr[i + 1], unordered inside)"""
-    _require_gpu(pos)
+    _require_gpu(pos)              # (ahead of the return that launches nothing)
     N = int(pos.shape[0])
-    assert radius.dtype == torch.float64 and radius.shape[0] == N and radius.is_contiguous()
-    assert cl.bin_atoms.dtype == torch.int64 and cl.bin_atoms.shape[0] == N and cl.bin_start.dtype == torch.int64 and cl.bin_start.shape[0] == cl.bins_cap + 1
+    assert radius.shape[0] == N and cl.bin_atoms.shape[0] == N and cl.bin_start.shape[0] == cl.bins_cap + 1
     if seg_ptr is None:
         out = torch.empty(N, device=pos.device, dtype=torch.int64)
         counts, keys = out, None
     else:
-        assert seg_ptr.dtype == torch.int64 and seg_ptr.shape[0] == N + 1 and seg_ptr.is_contiguous()
+        assert seg_ptr.shape[0] == N + 1
         out = torch.empty(int(capacity), device=pos.device, dtype=torch.int64)
         counts, keys = None, out
         if capacity == 0:
             return out
-    check(lib().hg_neighbour_pairs(ptr(pos), ptr(radius), ptr(batch), ptr(cl.cpar), ptr(cl.ipar), ptr(cl.bin_id), ptr(cl.wrap), ptr(cl.bin_start), ptr(cl.bin_atoms),
-                                   i64(N), i32(cl.B), i64(cl.bins_cap), ptr(seg_ptr), i64(capacity), ptr(counts), ptr(keys), ptr(flags), _stream()), "hg_neighbour_pairs")
+    call("hg_neighbour_pairs", pos, radius, batch, cl.cpar, cl.ipar, cl.bin_id, cl.wrap, cl.bin_start, cl.bin_atoms, N, cl.B, cl.bins_cap, seg_ptr, capacity, counts, keys, flags)
     return out
 
 
 @_on_tensor_device
 def neighbour_decode(keys: torch.Tensor, cell: torch.Tensor, batch, N: int):
     """hg_neighbour_decode: sorted packed keys -> (edge_index [2, E] int64, cell_shift [E, 3] int64, nbr_shift [E, 3] fp32 = S @ cell in fp64, rounded once)"""
-    _require_gpu(keys)
     E, dev = int(keys.shape[0]), keys.device
-    assert keys.dtype == torch.int64 and keys.is_contiguous() and cell.dtype == torch.float32 and cell.is_contiguous()
     ei = torch.empty(2, E, device=dev, dtype=torch.int64)
     cs = torch.empty(E, 3, device=dev, dtype=torch.int64)
     ns = torch.empty(E, 3, device=dev, dtype=torch.float32)
-    check(lib().hg_neighbour_decode(ptr(keys), i64(E), ptr(cell), ptr(batch), i64(N), i32(cell.shape[0]), ptr(ei), ptr(cs), ptr(ns), _stream()), "hg_neighbour_decode")
+    call("hg_neighbour_decode", keys, E, cell, batch, N, cell.shape[0], ei, cs, ns)
     return ei, cs, ns

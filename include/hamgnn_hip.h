@@ -118,7 +118,9 @@ int hg_tp_fused(const float* const* src, const int64_t* src_stride, int nsrc, co
  *   row_table   int32: per part, for every output row (segment, 16-row tile, row) of GEMM2 the LDS float offset (relative to a tile
  *               copy) of that row's centre column; rows beyond the segment's multiplicity point at the trash row
  *   part_table  int32[nparts][16] = {first segment, segments, first phase, phases, trash_off, stage_off, ctr_off, copy_stride,
- *               rowtab_off (LDS float offset of the part's copy of the row table), rowtab_begin, rowtab_len, lite flag, 0, 0, 0, 0}: the launch runs
+ *               rowtab_off (LDS float offset of the part's copy of the row table), rowtab_begin, rowtab_len, lite flag, [12] W3 split twins present (1: the
+ *               W3 blocks of `weights` are followed by the split-half-precision twins hg_w3_split_refill writes, and hg_tp_is forms the radial scale from them
+ *               when hidden == 64; 0: the fp32 form), [13] the twins' exponent (they hold w * 2^[13]), 0, 0}: the launch runs
  *               nparts sub-schedules (grid.y) that own disjoint sets of output segments; one part = the whole program, several
  *               parts spread a 16-edge tile's serial pass over several workgroups when there are fewer tiles than CUs (small
  *               crystals: BASELINE configs #1 and #5).  trash_off / stage_off / ctr_off: float offsets of the padding-row sink,

@@ -9,8 +9,6 @@ the `_slot`, `_cg`, `_mask`, `_blk` of a HamGNNPlusPlusOut); hand-made tables, v
 
 compare(out, ref, scale) is the measure: the largest per-row value of max_p |out - ref| / max_p scale, scale = the twin's sum of absolute terms (|ref| for
 element-wise operations).  The bound is gpu_checks.TOL, per row -- per irrep copy for the norm activation."""
-import contextlib
-import ctypes as C
 import functools
 import math
 import types
@@ -72,27 +70,6 @@ def to_dev(t, dev):
     base = t._base
     assert base is not None and base.is_contiguous()
     return torch.as_strided(base.to(dev), t.shape, t.stride(), t.storage_offset())
-
-
-@contextlib.contextmanager
-def strided_ok(B):
-    """The wrappers of hamgnn_amd.ops pass every row stride on to the C ABI, but their pointer helper insists on contiguous tensors; the kernels do not.  For
-    the strided cases the helper is relaxed to 'unit column stride' (what the kernels need), for the duration of the call."""
-    if not hasattr(B, "ptr"):
-        yield
-        return
-    old = B.ptr
-
-    def ptr(t):
-        if t is None:
-            return C.c_void_p(0)
-        assert t.numel() == 0 or t.stride(-1) == 1
-        return C.c_void_p(t.data_ptr())
-    B.ptr = ptr
-    try:
-        yield
-    finally:
-        B.ptr = old
 
 
 def sync(dev):
@@ -166,8 +143,7 @@ def check_segment_sum(case, B, dev, defect=None):
     if B is None:
         return {"err": compare(R.segment_sum(msg, rowptr, perm)[0], ref, scale)}
     a = [to_dev(t, dev) for t in (msg, rowptr, perm)]
-    with strided_ok(B):
-        out, same = twice(lambda: B.segment_sum(a[0], a[1], a[2], N), dev)
+    out, same = twice(lambda: B.segment_sum(a[0], a[1], a[2], N), dev)
     return {"err": compare(out, ref, scale), "exact": bool(torch.equal(out, segment_sum_fp32(msg, rowptr, perm))), "repeat": same}
 
 
@@ -264,8 +240,7 @@ def check_gate(case, B, dev, defect=None, backward=False):
         return {"err": compare(good, ref, scale)}
     xd, gyd, cd = to_dev(x, dev), to_dev(gy, dev), consts.to(dev)
     td = tuple(t.to(dev) for t in tabs)
-    with strided_ok(B):
-        out, same = twice((lambda: B.gate_backward(xd, gyd, td, cd)) if backward else (lambda: B.gate(xd, td, cd)), dev)
+    out, same = twice((lambda: B.gate_backward(xd, gyd, td, cd)) if backward else (lambda: B.gate(xd, td, cd)), dev)
     exact = bool((out[:, unread] == 0).all()) if backward else bool((out[:, zeros] == 0).all())
     return {"err": compare(out[idx], ref, scale), "exact": exact, "repeat": same}
 
@@ -336,8 +311,7 @@ def check_norm_act(case, B, dev, defect=None, backward=False):
     if B is None:
         return {"err": compare(by_channel(R.norm_act(x, tab), tab), by_channel(ref, tab), by_channel(scale, tab))}
     xd, gyd, td = to_dev(x, dev), to_dev(gy, dev), tab.to(dev)
-    with strided_ok(B):
-        out, same = twice((lambda: B.norm_act_backward(xd, gyd, td)) if backward else (lambda: B.norm_act(xd, td)), dev)
+    out, same = twice((lambda: B.norm_act_backward(xd, gyd, td)) if backward else (lambda: B.norm_act(xd, td)), dev)
     oc, rc, sc = by_channel(out, tab), by_channel(ref, tab), by_channel(scale, tab)
     res = {"err": compare(oc, rc, sc), "exact": bool((out[:, pad] == 0).all()), "repeat": same}
     for name, m in norm_subsets(x, tab).items():
@@ -408,8 +382,7 @@ def check_exact(case, B, dev):
     if not hasattr(B, op):                                     # (tests/cpu_ops.py has no stand-in for add_rows: nothing calls it on the CPU path)
         return {"err": compare(exact_fp32(case), twin, twin.abs()), "exact": True, "repeat": True}
     ad = [to_dev(t, dev) for t in a]
-    with strided_ok(B):
-        out, same = twice(lambda: getattr(B, op)(*ad), dev)
+    out, same = twice(lambda: getattr(B, op)(*ad), dev)
     return {"err": compare(out, twin, twin.abs()), "exact": bool(torch.equal(out, exact_fp32(case))), "repeat": same}
 
 
@@ -511,8 +484,7 @@ def check_attn_logits(case, B, dev, defect=None):
     if B is None:
         return {"err": compare(R.attn_logits(K, src[idx], dst[idx], length[idx], tab, H, hd, ATTN_CUT_PARAM, ATTN_CUTOFF)[0], ref, scale)}
     Kd, geo, td, cp = to_dev(K, dev), attn_geo(src, dst, length, dev), tab.to(dev), torch.tensor([ATTN_CUT_PARAM], dtype=F32).to(dev)
-    with strided_ok(B):
-        out, same = twice(lambda: B.attention_logits(Kd, geo, td, H, hd, cp, ATTN_CUTOFF), dev)
+    out, same = twice(lambda: B.attention_logits(Kd, geo, td, H, hd, cp, ATTN_CUTOFF), dev)
     zero = R.soft_cut(length, ATTN_CUT_PARAM, ATTN_CUTOFF) == 0
     return {"err": compare(out[idx], ref, scale), "exact": bool((out[zero] == 0).all()), "repeat": same, "logits": out}
 
@@ -526,8 +498,7 @@ def check_attn_aggregate(case, B, dev, defect=None, logits=None):
     if B is None:
         return {"err": compare(R.attn_aggregate(lg, V, rowptr, perm, tab, H)[0], ref, scale)}
     Kd, Vd, geo, td, cp = to_dev(K, dev), to_dev(V, dev), attn_geo(src, dst, length, dev), tab.to(dev), torch.tensor([ATTN_CUT_PARAM], dtype=F32).to(dev)
-    with strided_ok(B):
-        out, same = twice(lambda: B.attention_aggregate(Kd, Vd, geo, rowptr.to(dev), perm.to(dev), td, H, hd, cp, ATTN_CUTOFF), dev)
+    out, same = twice(lambda: B.attention_aggregate(Kd, Vd, geo, rowptr.to(dev), perm.to(dev), td, H, hd, cp, ATTN_CUTOFF), dev)
     deg0 = (rowptr[1:] == rowptr[:-1])
     return {"err": compare(out, ref, scale), "exact": bool((out[deg0] == 0).all() and (out[:, tab < 0] == 0).all()), "repeat": same}
 
@@ -666,8 +637,7 @@ def check_ham_readout(case, B, dev, defect=None, two_launches=False):
             return B.ham_finish(raw, inv, d["H0"], d["mask"], d["z"], d["ia"], d["ib"], nao, a["sign"], a["sym"], a["h0_last"])
         out = torch.full((rows, nao * nao), float("nan"), dtype=F32).to(dev)
         return B.ham_readout(d["coeff"], geo, *tabs, nao, pairs, d["H0"], d["mask"], d["z"], d["ia"], d["ib"], out, a["lmax"], a["sign"], a["sym"], a["h0_last"])
-    with strided_ok(B):
-        out, same = twice(run, dev)
+    out, same = twice(run, dev)
     return {"err": compare(out[idx], ref, scale), "exact": bool(torch.isfinite(out).all()), "repeat": same}
 
 
@@ -757,8 +727,7 @@ def check_soc(case, B, dev, defect=None):
         cat = lambda t: torch.cat(t, 1) if isinstance(t, tuple) else t
         return {"err": compare(cat(good), cat(ref), cat(scale))}
     ad = [to_dev(t, dev) for t in a]
-    with strided_ok(B):
-        out, same = twice(lambda: getattr(B, op)(*ad), dev)
+    out, same = twice(lambda: getattr(B, op)(*ad), dev)
     if op == "block_mean":
         return {"err": compare(out, ref, scale), "exact": True, "repeat": same}
     return {"err": max(compare(o, r, s) for o, r, s in zip(out, ref, scale)), "exact": True, "repeat": same}
