@@ -34,6 +34,8 @@ __device__ __forceinline__ f32x4 hg_mfma_f32_16x16x4(float a, float b, f32x4 c) 
 #define SEG_UNROTATE 1
 #define SEG_ATOMIC 2             // (split launches only) the segment is one of TWO copies that share an output block: each adds its half of the items' sum
                                  // (plan.split_heavy_segments: the heaviest output irreps of a small crystal's launch on two workgroups; the rows are zero-filled by the host)
+#define SEG_CENTRE 4             // (input-stationary schedule, un-rotated segments with l > 0) only the centre column (m = 0) of the tile is ever written: the
+                                 // epilogue un-rotates that column alone, from row l of the Wigner block (plan/schedule_is.py)
 
 // phase profiler of the edge kernels (HG_PROF builds only, tests/bench_tp.py --prof): per-wave shader-clock time between probes, summed over
 // waves into the kernel's own __device__ array (hg_prof_read / hg_prof_is_read)

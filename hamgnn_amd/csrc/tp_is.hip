@@ -939,8 +939,11 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
                     const int l2 = T8[0];
                     if (!(T8[7] & SEG_UNROTATE) || l2 == lprev) continue;      // one block per l (segments are ordered by batch, l)
                     lprev = l2;
-                    const int nn = (2 * l2 + 1) * (2 * l2 + 1);
-                    const float* __restrict__ D = A.wig + erow * A.nW + hg_pick8(A.wig_off, l2);
+                    // centre-only segments (SEG_CENTRE: the same for every un-rotated segment of one l in a part) read row l2 of the block alone: 2 l2 + 1
+                    // values per edge instead of (2 l2 + 1)^2, image [a][edge]
+                    const bool cen = l2 > 0 && (T8[7] & SEG_CENTRE);
+                    const int nn = cen ? 2 * l2 + 1 : (2 * l2 + 1) * (2 * l2 + 1);
+                    const float* __restrict__ D = A.wig + erow * A.nW + hg_pick8(A.wig_off, l2) + (cen ? l2 * (2 * l2 + 1) : 0);
                     const int nj = (nn + 3) >> 2;
 #pragma unroll 1
                     for (int j = wave; j < nj; j += NW) {      // image [m * NCO + a][edge]

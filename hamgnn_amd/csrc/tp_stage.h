@@ -121,7 +121,27 @@ __device__ __forceinline__ void epilogue_is(const IsArgs& A, const float* __rest
     const int u_begin = wave * per, u_end = (u_begin + per) < U ? (u_begin + per) : U;
     // a lane owns FOUR consecutive channels of one (edge, component): 4 NCO tile reads in flight, one 16-byte store -- a wave writes 16 edges x
     // 64 contiguous bytes per request (r3: a dword per lane, four requests for the same bytes)
-    if (flags & SEG_UNROTATE) {
+    if (LK > 0 && (flags & SEG_UNROTATE) && (flags & SEG_CENTRE)) {
+        // every item that fed this tile wrote its centre column (m = 0) only (plan/schedule_is.py: SEG_CENTRE; the first ConvBlock of a backbone, whose node rows
+        // are 0e and whose edge rows hold the m = 0 component of Y^l): out[a] = D[LK][a] t[LK] -- one tile read and one product per channel where the full
+        // un-rotation takes 2 LK + 1, and the kernel has staged row LK of the Wigner block alone: image [a][edge]
+        const float* __restrict__ dl = dstage + el;
+        const float* __restrict__ tc = tl + LK * 16;
+#pragma unroll 1
+        for (int u = u_begin; u < u_end; ++u) {
+            const int a = u / nw16, w = (u - a * nw16) * 16 + 4 * g;
+            if (w >= wend) continue;
+            const float dc = dl[a * 16];
+            f32x4 acc;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = w + k < mul_k ? dc * tc[(w + k) * rowstride] : 0.f;
+            if (red) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = is_seg_scan(acc[k], sc);
+            }
+            if (valid) is_store4<AT>(ob + a * out_mulp + w, acc, flags);
+        }
+    } else if (flags & SEG_UNROTATE) {
         const float* __restrict__ dl = dstage + el;
 #pragma unroll 1
         for (int u = u_begin; u < u_end; ++u) {

@@ -83,6 +83,13 @@ class _BackboneBase(hnn.CompiledModule, nn.Module):
         sh = {(l, p) for _, l, p in Irreps(self.irreps_edge_sh)}
         return (tuple(i for i, (_, l, p) in enumerate(irr) if (l, p) != (0, 1)), tuple(i for i, (_, l, p) in enumerate(irr) if (l, p) not in sh))
 
+    def _centre_edge_set(self):
+        """edge irreps that are non-zero only in their CENTRE component (m = 0) in the rows the first layer reads: the pair embedding's edge rows are written
+        in the edge-aligned frame, where Y^l has its m = 0 component only (0e (x) Y^l keeps it, and so do the same-irrep Linears behind it)"""
+        from ..so3 import Irreps
+        sh = {(l, p) for _, l, p in Irreps(self.irreps_edge_sh)}
+        return tuple(i for i, (_, l, p) in enumerate(Irreps(self.irreps_node_features)) if (l, p) in sh and l > 0)
+
     def _init_common(self, config):
         c = _cfg_get(config, "HamGNN_pre", config)
         g = lambda k, d=None: _cfg_get(c, k, d)
@@ -425,12 +432,13 @@ class HamGNNConvE3(_BackboneBase):
         ConvBlock launch and 20 % of the first PairInteractionBlock launch for the shipped irreps).  The node rows are full after the first ConvBlock,
         the edge rows after the first PairInteractionBlock that updates them (a legacy layer-0 block does not: interaction_blocks.py:154-160)."""
         zero_node, zero_edge = self._structural_zero_sets()
+        centre_edge = self._centre_edge_set()                  # the irreps that do carry a Y^l: its m = 0 component only (one column instead of 2 l + 1)
         for conv, pair in zip(self.convolutions, self.pair_interactions):
-            conv.conv_tp.set_structural_zeros(node=zero_node, edge=zero_edge)
+            conv.conv_tp.set_structural_zeros(node=zero_node, edge=zero_edge, centre_edge=centre_edge)
             zero_node = ()
             if pair.use_skip_connections or not pair.legacy_edge_update:
-                pair.conv_tp.set_structural_zeros(node=(), edge=zero_edge)
-                zero_edge = ()
+                pair.conv_tp.set_structural_zeros(node=(), edge=zero_edge, centre_edge=centre_edge)
+                zero_edge = centre_edge = ()
 
     def _blocks(self):
         return [*self.convolutions, *(self.corr_products if self.use_corr_prod else ()), *self.pair_interactions]
@@ -448,6 +456,10 @@ class HamGNNConvE3(_BackboneBase):
                 for i in idx:
                     o, w = self.layout.off[i], (2 * self.layout.irreps[i][1] + 1) * self.layout.mulp[i]
                     assert float(rows[:, o:o + w].abs().max()) == 0.0, ("structural zero violated", i)
+            for i in self._centre_edge_set():                  # ... and the irreps of the spherical harmonics hold their m = 0 component only
+                o, l, mp = self.layout.off[i], self.layout.irreps[i][1], self.layout.mulp[i]
+                for a in range(2 * l + 1):
+                    assert a == l or float(f[:, o + a * mp:o + (a + 1) * mp].abs().max()) == 0.0, ("centre-only edge irrep violated", i, a - l)
         rowptr, perm = topo.receiver_csr()
         tape = [] if save_for_backward else None
         # the last PairInteractionBlock may leave out the irreps its declared consumer never reads (declare_consumer)

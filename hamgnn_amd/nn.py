@@ -364,7 +364,7 @@ class MessagePackBlock(DeviceState, nn.Module):
             self.edge_weight_generator = _weight_generator([num_radial] + list(radial_MLP) + [self.edge_linear_scaler.weight_numel], self.use_kan)
             self.node_linear_out = E3Linear(self.irreps_out, self.irreps_out)
             self.edge_linear_out = E3Linear(self.irreps_out, self.irreps_out)
-        self._zeros, self._dead = ((), ()), ()                 # set_structural_zeros / set_dead_outputs: read by the next compile()
+        self._zeros, self._dead, self._centre = ((), ()), (), ()     # set_structural_zeros / set_dead_outputs: read by the next compile()
         # structural (depend on the irreps only), survive recompiles: the packers by tag, the L' block-GEMM units, the rotate table of the output rows
         self._packers, self._bg_lp, self._rt_out = {}, None, None
         self._wg = self._wg_prev = None                        # backward_mp.MessagePackWeightGrad of the compiled weights (built on first use), and the one before
@@ -399,11 +399,14 @@ class MessagePackBlock(DeviceState, nn.Module):
     _wgrad_fused_z = property(lambda self: self.programs().get(("wgrad fused", True)))
     _wgrad = property(lambda self: self._wg and [self._wg, self.programs().get(("wgrad rows", "A")), self.programs().get(("wgrad rows", "B"))])
 
-    def set_structural_zeros(self, node=(), edge=()):
+    def set_structural_zeros(self, node=(), edge=(), centre_edge=()):
         """irreps (indices into irreps_node / irreps_edge) whose rows are STRUCTURALLY zero where this block runs (the first layer: node rows out of an
         o3.Linear from 0e scalars, edge rows out of the pair embedding's 0e x Y^l product): the forward program drops the super-paths that read them
-        (plan.build_message_pack_program).  Takes effect at the next compile(); the backward programs stay complete (they produce the zeros)."""
+        (plan.build_message_pack_program).  centre_edge: edge irreps whose rows are non-zero only in their centre component (m = 0) there -- the pair
+        embedding's Y^l in the edge frame: one column of their even super-paths is issued, their odd super-paths are dropped.
+        Takes effect at the next compile(); the backward programs stay complete (they produce the zeros)."""
         self._zeros = (tuple(sorted(int(i) for i in node)), tuple(sorted(int(i) for i in edge)))
+        self._centre = tuple(sorted(int(i) for i in centre_edge))
         return self
 
     def set_dead_outputs(self, out=()):
@@ -415,13 +418,16 @@ class MessagePackBlock(DeviceState, nn.Module):
 
     def _zero_kw(self):
         """what the REDUCED forward program of this block may assume (plan.build_message_pack_program): structurally zero input irreps, unread output irreps.
-        HG_STRUCT_ZEROS / HG_DEAD_OUT are compile-time switches: read here, by compile(), and recorded in _zkw_compiled"""
+        HG_STRUCT_ZEROS / HG_CENTRE_ZEROS / HG_DEAD_OUT are compile-time switches: read here, by compile(), and recorded in _zkw_compiled
+        (HG_STRUCT_ZEROS=0 switches both input shortcuts off, HG_CENTRE_ZEROS=0 the centre-only columns alone: the programs of the irrep-level shortcut)"""
         zn, ze = self._zeros
         if self.lite_mode:
             return {}
         kw = {}
         if os.environ.get("HG_STRUCT_ZEROS", "1") != "0" and (zn or ze):
             kw.update(zero_node=zn, zero_edge=ze)
+        if os.environ.get("HG_STRUCT_ZEROS", "1") != "0" and os.environ.get("HG_CENTRE_ZEROS", "1") != "0" and self._centre:
+            kw["centre_edge"] = self._centre
         if os.environ.get("HG_DEAD_OUT", "1") != "0" and self._dead:
             kw["dead_out"] = self._dead
         return kw
@@ -431,9 +437,9 @@ class MessagePackBlock(DeviceState, nn.Module):
         reads the gradient of a structurally zero input), as compiled"""
         return {k: v for k, v in self._zkw_compiled.items() if k in ("zero_node", "zero_edge")}
 
-    def _ztag(self, n=3):
+    def _ztag(self, n=4):
         z = self._zkw_compiled
-        return ((z.get("zero_node", ()), z.get("zero_edge", ()), z.get("dead_out", ()))[:n],)
+        return ((z.get("zero_node", ()), z.get("zero_edge", ()), z.get("dead_out", ()), z.get("centre_edge", ()))[:n],)
 
     def _upload(self, key, tag, build, upload, uses_skip=False, sd=None, host=None):
         """build the program `key` and upload it; sd: the state dict if the caller has just read it, None: read here -- always the weights of the
@@ -495,7 +501,9 @@ class MessagePackBlock(DeviceState, nn.Module):
             self._groups = self._groups_z = P.choose_merge_groups(*irr, hidden)
             if self._groups:
                 try:
-                    if zkw.get("dead_out"):                    # output irreps nobody reads leave the row-tile groups
+                    if zkw.get("centre_edge"):                 # one-column items stack whatever their l: the groups are chosen for the items the reduced program has
+                        self._groups_z = P.choose_merge_groups(*irr, hidden, **zkw) or self._groups
+                    elif zkw.get("dead_out"):                  # output irreps nobody reads leave the row-tile groups
                         self._groups_z = P.choose_merge_groups(*irr, hidden, dead_out=zkw["dead_out"])
                     self._dp = self._upload_forward(False, False, sd)
                     if zkw:                                    # the same block for rows whose marked irreps are structurally zero (first layer of a backbone) /

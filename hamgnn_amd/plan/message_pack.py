@@ -104,30 +104,37 @@ def kan_pack_hidden(layers):
 
 
 @single_thread_blas
-def choose_merge_groups(irreps_node, irreps_edge, irreps_sh, irreps_out, hidden: int, dead_out: Sequence[int] = ()) -> List[List[int]]:
+def choose_merge_groups(irreps_node, irreps_edge, irreps_sh, irreps_out, hidden: int, dead_out: Sequence[int] = (), zero_node: Sequence[int] = (),
+                        zero_edge: Sequence[int] = (), centre_edge: Sequence[int] = ()) -> List[List[int]]:
     """Which small output irreps share their MFMA row tiles (add_tp_items merge_groups): per parity class (l + [p odd]) mod 2, the
     partition of the irreps with <= 16 channels that minimises the issued MFMAs of the block (exhaustive over the handful of
     candidates; cost = the planner's own count: radial scale + GEMM1 + GEMM2 per super-path, node and edge branch).  dead_out: output irreps the
-    program does not compute (build_message_pack_program): never grouped."""
+    program does not compute (build_message_pack_program): never grouped.  zero_node / zero_edge / centre_edge: what the program assumes about its input rows
+    (build_message_pack_program) -- super-paths it does not emit cost nothing, a centre-only edge irrep has one column and stacks whatever its l."""
     irreps_node, irreps_edge, irreps_sh, irreps_out = Irreps(irreps_node), Irreps(irreps_edge), Irreps(irreps_sh), Irreps(irreps_out)
     dead_out = set(int(k) for k in dead_out)
     H4 = ceil_div(hidden, 16) * 4
     branches = []
-    for nsrc, irr in ((2, irreps_node), (1, irreps_edge)):
+    for nsrc, irr, zero, centre in ((2, irreps_node, zero_node, ()), (1, irreps_edge, zero_edge, centre_edge)):
         irr_in = Irreps([(m * nsrc, l, p) for m, l, p in irr])
         ins = tp_instructions(irr_in, irreps_sh, irreps_out)
+        zero, centre = set(int(i) for i in zero), set(int(i) for i in centre)
         npath: Dict[Tuple[int, int], int] = {}
         for (i, j, k, slot) in ins:
+            odd = (irr_in[i][1] + irreps_sh[j][1] + irreps_out[k][1]) % 2
+            if i in zero or (i in centre and irr_in[i][1] > 0 and odd):       # not emitted
+                continue
             npath[(i, k)] = npath.get((i, k), 0) + 1
-        branches.append((nsrc, PlanarLayout(irr), irr_in, npath))
+        branches.append((nsrc, PlanarLayout(irr), irr_in, npath, centre))
 
     def cost(groups):
         tot = 0
         for G in groups:
             lmin = min(irreps_out[k][1] for k in G)
             rto = ceil_div(sum(irreps_out[k][0] for k in G), 16)
-            for nsrc, lay, irr_in, npath in branches:
+            for nsrc, lay, irr_in, npath, centre in branches:
                 for i, (mi2, li, pi) in enumerate(irr_in):
+                    li = 0 if i in centre else li               # (one column)
                     if li <= lmin and len(G) > 1:
                         stacks = [(sum(npath.get((i, k), 0) * irreps_out[k][0] for k in G), li, rto)]
                     else:
@@ -162,7 +169,8 @@ def choose_merge_groups(irreps_node, irreps_edge, irreps_sh, irreps_out, hidden:
 @single_thread_blas
 def build_message_pack_program(sd: Dict[str, np.ndarray], irreps_node, irreps_edge, irreps_sh, irreps_out, unrotate: bool,
                                skip_weight: Optional[np.ndarray] = None, merge_groups: Sequence[Sequence[int]] = (),
-                               zero_node: Sequence[int] = (), zero_edge: Sequence[int] = (), dead_out: Sequence[int] = ()) -> Program:
+                               zero_node: Sequence[int] = (), zero_edge: Sequence[int] = (), dead_out: Sequence[int] = (),
+                               centre_edge: Sequence[int] = ()) -> Program:
     """MessagePackBlock (non-lite, message_passing.py:216-229) [+ the PairInteractionBlock skip o3.Linear on the edge
     features, interaction_blocks.py:151-152] as ONE fused-kernel program.  `sd`: reference-named arrays of the block.
     zero_node / zero_edge (r5): irreps of the node / edge feature rows that are STRUCTURALLY zero where this block runs -- the first layer reads node rows
@@ -170,6 +178,11 @@ def build_message_pack_program(sd: Dict[str, np.ndarray], irreps_node, irreps_ed
     0e (x) Y^l product (only the irreps of the spherical harmonics: embeddings.py:310-337).  The reference multiplies those zeros through every path
     (message_passing.py:216-229); here the super-paths (and skip-Linear paths) that read them are not emitted: same rows, bit for bit in exact arithmetic,
     because a dropped item would have added +0.0 to its tile cells.
+    centre_edge: edge irreps whose rows are non-zero only in their CENTRE component (m = 0) where this block runs -- the pair embedding writes 0e (x) Y^l in
+    the edge-aligned frame, where Y^l has its m = 0 component only, and same-irrep Linears keep that.  The aligned-frame coupling is diagonal in m (m -> -m
+    for odd super-paths, whose centre coefficient vanishes), so such a block reaches centre columns only: its even super-paths (and skip-Linear paths) are
+    emitted with ONE column over the centre component alone, its odd super-paths not at all (add_tp_items: centre_inputs).  Exact for the same reason as
+    above: the columns left out would have added +0.0.
     dead_out (r5): output irreps whose rows NOBODY reads where this block runs -- the edge rows of the last PairInteractionBlock feed only the read-out head,
     whose o3.Linear / Gate chain connects equal (l, p) only (hamgnn_output.py:38-58: it reads the irreps of the Hamiltonian blocks + the 0e gate scalars;
     e.g. 0o, 4o, 5o, 5e, 6e of the shipped set are never read for nao_max 19).  Their super-paths and skip-Linear paths are not emitted and their blocks of
@@ -187,9 +200,10 @@ def build_message_pack_program(sd: Dict[str, np.ndarray], irreps_node, irreps_ed
     add_tp_items(prog, seg_of_k, PlanarLayout(irreps_edge), 1, [SRC_F], irreps_sh, irreps_out,
                  np.asarray(sd["edge_tensor_product.weight"]), w3e,
                  np.asarray(sd["edge_linear_scaler.linear_out.weight"]), np.asarray(sd["edge_linear_out.weight"]), mlp=1,
-                 merge_groups=merge_groups, zero_inputs=zero_edge, dead_out=dead_out)
+                 merge_groups=merge_groups, zero_inputs=zero_edge, dead_out=dead_out, centre_inputs=centre_edge)
     if skip_weight is not None:
-        add_linear_items(prog, seg_of_k, PlanarLayout(irreps_edge), SRC_F, irreps_out, np.asarray(skip_weight), zero_inputs=zero_edge, dead_out=dead_out)
+        add_linear_items(prog, seg_of_k, PlanarLayout(irreps_edge), SRC_F, irreps_out, np.asarray(skip_weight), zero_inputs=zero_edge, dead_out=dead_out,
+                         centre_inputs=centre_edge)
     return prog.finalize()
 
 

@@ -223,6 +223,7 @@ KERNEL_RTM_MAX = (4, 4, 3, 2, 2, 1, 1)
 
 def _add_item(prog: Program, seg, typ, srcs, in_off, in_mulp, li, mm, neg, ksteps, rtm, mlp, a1, w3, cf, a2, nrows, row_off=0, nk2=None, rto=None):
     assert len(srcs) in (1, 2)
+    assert not (neg and mm == 0), "an odd item with one column: the kernels have no ODD case at MM = 0 and would skip it silently"
     if typ != IT_POST and not (0 <= mm < len(KERNEL_RTM_MAX) and 1 <= rtm <= KERNEL_RTM_MAX[mm]):
         raise NotImplementedError(f"no kernel instantiation for an item with min(l_in, l_out) = {mm} and {rtm} row tiles")
     nk2 = 4 * rtm if nk2 is None else nk2                      # GEMM2 K-steps actually issued (item[18])
@@ -364,16 +365,20 @@ def _tp_superpaths(nsrc: int, in_layout: PlanarLayout, irreps_sh: Irreps, irreps
 def add_tp_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarLayout, nsrc: int, srcs: Sequence[int],
                  irreps_sh: Irreps, irreps_out: Irreps, tp_weight: np.ndarray, w3: np.ndarray, lin_scale_w: np.ndarray,
                  lin_out_w: Optional[np.ndarray], mlp: int, uvu: bool = False, merge_groups: Sequence[Sequence[int]] = (), zero_inputs: Sequence[int] = (),
-                 dead_out: Sequence[int] = ()):
+                 dead_out: Sequence[int] = (), centre_inputs: Sequence[int] = ()):
     """Items of ONE reference tensor-product branch (node or edge) of a MessagePackBlock / embedding TP.
     dead_out: output irreps (indices into irreps_out) nobody reads where this block runs -- their super-paths are dropped and their tiles are written as
     zeros (see build_message_pack_program); a merge group must not contain one (choose_merge_groups(dead_out=...)).
     zero_inputs: input irreps (indices into in_layout.irreps) whose rows are STRUCTURALLY zero for this block -- every super-path that reads one of
     them contributes exactly nothing and is dropped (see build_message_pack_program).
+    centre_inputs: input irreps whose rows are non-zero only in their CENTRE component (m = 0) for this block (see build_message_pack_program: centre_edge)
+    -- the aligned-frame coupling is diagonal in m, so an even super-path that reads one feeds the centre column of its target only: it becomes an item with ONE
+    column (mm = 0, the centre coefficient) over the centre component as a block of its own (l = 0 at the component's offset, so the kernels stage that
+    component alone); an odd super-path (m -> -m, centre coefficient zero) contributes nothing and is dropped.  Single-source branches only.
     merge_groups: lists of output irreps k whose super-paths from one input irrep are stacked into ONE item (see Program.vsegs):
     the rows of a 16-row MFMA tile are then filled by several small output irreps instead of one (4x5o alone uses 12 of 16 rows of
     GEMM1 / the radial scale and 4 of 16 rows of GEMM2's output).  Only super-paths with l_i <= min l_k of the group are stacked (same
-    column count 2 l_i + 1); the members must share the parity class (l_k + [p_k odd]) mod 2 so that `par` agrees.
+    column count 2 l_i + 1; a centre-only input has one column whatever its l); the members must share the parity class (l_k + [p_k odd]) mod 2 so that `par` agrees.
 
     in_layout : planar layout of ONE source row (irreps of the un-doubled features); nsrc = 2 for the node branch
                 (reference input = (2 mul) x ir with the first mul channels from src, the rest from dst: attention_utils.py:85-119).
@@ -399,10 +404,19 @@ def add_tp_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarLayou
     plain: List[dict] = []
     zero_inputs = set(int(i) for i in zero_inputs)
     dead_out = set(int(k) for k in dead_out)
+    centre_inputs = set(int(i) for i in centre_inputs) - zero_inputs
+    assert not centre_inputs or (nsrc == 1 and not uvu), "centre-only inputs: the edge branch of a weighted tensor product"
     assert not (dead_out & set(group_of)), "a merge group holds a dead output irrep"
     for sp in _tp_superpaths(nsrc, in_layout, irreps_sh, irreps_out, tp_weight, w3, lin_scale_w, lin_out_w, uvu):
         if sp["i"] in zero_inputs or sp["k"] in dead_out:
             continue
+        if sp["i"] in centre_inputs and sp["li"] > 0:
+            if sp["par"]:                                      # odd: antisymmetric in m, nothing reaches any column from the centre component
+                assert not sp["cf"][:, sp["mm"]].any()
+                continue
+            nc_ = 2 * sp["mm"] + 1                             # (every term of the flop count carries the column count)
+            sp = dict(sp, in_off=in_layout.off[sp["i"]] + sp["li"] * in_layout.mulp[sp["i"]], li=0, cf=sp["cf"][:, sp["mm"]:sp["mm"] + 1], mm=0,
+                      flops=sp["flops"] / nc_)
         gi = group_of.get(sp["k"])
         if gi is not None and sp["li"] <= lmin[gi]:
             stacked.setdefault((sp["i"], gi), []).append(sp)
@@ -464,7 +478,7 @@ def add_tp_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarLayou
             # A2[rt'][rt][lane][r]: L'[row = 16 rt + 4 (lane>>4) + r][w'' = 16 rt' + (lane&15)]
             a2 = Lp.reshape(rtm, 4, 4, rto, 16).transpose(3, 0, 1, 4, 2).reshape(rto, rtm, 64, 4)
             a2_off = prog.add_weights(a2)
-            _add_item(prog, seg, IT_TP, list(srcs), in_layout.off[i], in_layout.mulp[i], li, mm, par, ksteps, rtm, mlp,
+            _add_item(prog, seg, IT_TP, list(srcs), sp.get("in_off", in_layout.off[i]), in_layout.mulp[i], li, mm, par, ksteps, rtm, mlp,
                       a1_off, w3_off, cf_off, a2_off, n, row_off=0 if vid is None else vid + 1, nk2=ceil_div(n, 4), rto=rto)
 
 
@@ -522,11 +536,14 @@ def add_tp_adjoint_items(prog: Program, in_layout: PlanarLayout, nsrc: int, src_
 
 
 def add_linear_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarLayout, src: int, irreps_out: Irreps,
-                     weight: np.ndarray, extra_scale: float = 1.0, zero_inputs: Sequence[int] = (), dead_out: Sequence[int] = ()):
+                     weight: np.ndarray, extra_scale: float = 1.0, zero_inputs: Sequence[int] = (), dead_out: Sequence[int] = (),
+                     centre_inputs: Sequence[int] = ()):
     """Items of one o3.Linear(irreps_in -> irreps_out) (e3nn: paths ordered by (i_in, i_out), 1/sqrt(fan_in)); zero_inputs: structurally zero input
-    irreps, dead_out: output irreps nobody reads -- their paths are dropped (the weights are still walked: the flat layout is the reference's)."""
+    irreps, dead_out: output irreps nobody reads -- their paths are dropped (the weights are still walked: the flat layout is the reference's).
+    centre_inputs: input irreps that are non-zero only in their centre component (add_tp_items) -- that component alone, into the centre column."""
     zero_inputs = set(int(i) for i in zero_inputs)
     dead_out = set(int(k) for k in dead_out)
+    centre_inputs = set(int(i) for i in centre_inputs)
     irr_in = in_layout.irreps
     paths = [(i, k) for i, (_, li, pi) in enumerate(irr_in) for k, (_, lk, pk) in enumerate(irreps_out) if (li, pi) == (lk, pk)]
     fan = {}
@@ -541,6 +558,9 @@ def add_linear_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarL
         if i in zero_inputs or k in dead_out:
             continue
         ksteps = in_layout.mulp[i] // 4
+        in_off = in_layout.off[i]
+        if i in centre_inputs:                                 # the centre component as a block of its own: one column
+            in_off, li = in_off + li * in_layout.mulp[i], 0
         # rows chunked like TP items so that the per-wave register budget is the same
         nc = 2 * li + 1
         chunk = rtm_max(nc) * 16
@@ -550,7 +570,7 @@ def add_linear_items(prog: Program, seg_of_k: Dict[int, int], in_layout: PlanarL
                 r1 = min(c1 - c0, r0 + chunk)
                 rtm = ceil_div(r1 - r0, 16)
                 a1_off = prog.add_weights(_frag_A(W[:, r0:r1], ksteps, rtm, use_x4(in_layout.mulp[i], nc))[None])
-                _add_item(prog, seg, IT_LIN, [src], in_layout.off[i], in_layout.mulp[i], li, li, 0, ksteps, rtm, 0,
+                _add_item(prog, seg, IT_LIN, [src], in_off, in_layout.mulp[i], li, li, 0, ksteps, rtm, 0,
                           a1_off, 0, 0, 0, r1 - r0, row_off=r0)
         prog.flops_per_row += 2.0 * mi * mk * nc
     assert off == weight.size, (off, weight.size)

@@ -84,6 +84,20 @@ def _item_cost(rec, segs, hp4, vsegs=()):
 
 
 SEG_ATOMIC = 2       # (split launches) one of the copies of an output segment that share its block of the rows: the epilogue ADDS (csrc/tp_stage.h)
+SEG_CENTRE = 4       # un-rotated segment with l > 0 whose items all have ONE column (mm = 0): only the centre column of its tile is ever written, the epilogue
+#                      un-rotates that column alone (out[a] = D[l][a] t[l]) from row l of the Wigner block, the only row the kernel then stages.  Set for all
+#                      un-rotated segments of one l in a part or for none (they share the staged block).  The tile keeps its full width.
+
+
+def _centre_segments(prog: "Program", members: List[int]) -> set:
+    """the segments of `members` that may carry SEG_CENTRE: every item that writes them (merged items: all their members) has mm = 0"""
+    full = set()
+    for rec in prog.item_table:
+        if int(rec[6]) > 0 or int(rec[0]) not in (IT_TP, IT_LIN):
+            full.update(prog.vsegs[int(rec[16]) - 1] if (int(rec[0]) == IT_TP and int(rec[16]) > 0) else [int(rec[19])])
+    cand = {m for m in members if int(prog.seg_table[m][7]) & SEG_UNROTATE and int(prog.seg_table[m][0]) > 0}
+    mixed_l = {int(prog.seg_table[m][0]) for m in cand if m in full}
+    return {m for m in cand if int(prog.seg_table[m][0]) not in mixed_l}
 
 
 def lds_partition(prog: "Program") -> List[int]:
@@ -360,6 +374,8 @@ def _is_schedule_part(prog: "Program", members: List[int], hp4: int, seg_base: i
     into the concatenated tables of the launch (bases given)."""
     segs = prog.seg_table[members].copy()
     local = {old: n for n, old in enumerate(members)}
+    for m in _centre_segments(prog, members):
+        segs[local[m]][7] |= SEG_CENTRE
     off, maxstride = 0, 0
     for s in segs:
         lk, mul_k = int(s[0]), int(s[1])
