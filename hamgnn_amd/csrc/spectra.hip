@@ -3,6 +3,7 @@
 //   hg_dos_broaden:      D[j, g] = sum_s A(E_j, eps_s) W[s, g], A a normalised Gaussian: a GEMM whose left operand is generated in registers
 //   hg_dos_tetra:        the same GEMM with the linear tetrahedron method's corner weights (DOS or number of states) as the left operand
 //   hg_bond_weights:     per-state bond weights (COOP / COHP), w[s, g] = wk[s] * sum_{bonds of g} Re(phase c_i^+ X_bond c_j) from the real-space rows
+//   hg_density_rows:     the density matrix sampled on the rows of the crystal graph, P[e][a, b] = sum_s f_s Re(phase conj(c_ia) c_jb): an SDDMM over the states
 // No atomics, no claim-order reduction: all kernels are bit-reproducible from launch to launch.  Callers allocate everything.
 #include "hg_device.h"
 
@@ -521,4 +522,164 @@ extern "C" int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t*
     else HG_BOND_LAUNCH(3);
 #undef HG_BOND_LAUNCH
     return hg_check_launch("hg_bond_weights");
+}
+
+// ------------------------------------------------------------------------------------------------ density-matrix rows
+// P_off[e][a, b] (+)= sum_s f_s Re(exp(2 pi i k_s . shift_e) conj(C[s][mu(i, a)]) C[s][mu(j, b)]),  P_on[i][a, b] the same with j = i and no phase; (i, j) =
+// (erow[e], ecol[e]) and mu(i, a) = ooff[i] + orank[i][a] as above.  A sampled dense-dense product (SDDMM): per member (an edge or an atom) an n_i x n_j
+// block with K = the states.  One workgroup owns one member (blocks 0 .. E - 1 the edges, E .. E + n_atoms - 1 the atoms); the steps of 4 states (one
+// v_mfma_f32_16x16x4_f32 each) are dealt to the 4 waves in contiguous quarters.  The block is tiled over the COMPACT ranks r = orank[i][a] (tiles of 16, NT x NT
+// accumulators): lane l holds A[r_a = 16 t + (l & 15)][state l >> 4] = f_s (x, y) of C[s][ooff[i] + r_a] and B[state l >> 4][r_b = 16 t + (l & 15)] =
+// (x', y') = exp(i theta) C[s][ooff[j] + r_b] -- the column operand is rotated once per loaded element, so that Re(phase conj(c_a) c_b) = x_a x'_b + y_a y'_b is
+// two real MFMA chains per tile instead of four; 16 lanes read 128 contiguous bytes of a row of C.  cos / sin of theta = 2 pi k . shift are formed once per
+// (k-point, member) in a prologue (k . shift and sincos in double, rounded once, as hk_pairs_kernel) into a table in LDS of the first DR_KCAP k-points; a
+// state whose k-point lies beyond the table forms its own (the slow path of a very large k-list).  Ranks past n_i / n_j and state slots past ns contribute
+// operands of 0 (their loads are redirected into range).  The waves' partial tiles go to LDS; the epilogue walks the nao x nao row as it lies in memory
+// (coalesced), maps (a, b) to its ranks and adds the four partials as ((w0 + w1) + w2) + w3: one owner per element, a fixed order, no atomics.  accumulate
+// 0: every element of the row is written, 0 where an atom lacks the orbital; 1: added to what is there, missing-orbital elements untouched.  A member's
+// block does not depend on the other members of the launch.  Every table entry is clamped into range before it indexes anything.
+#define DR_KCAP 1024                                         // k-points whose phase of the member is tabulated in LDS (8 KiB)
+template <int NT>
+__global__ __launch_bounds__(256) void density_rows_kernel(const float2* __restrict__ Cm, int ns, int M, const int32_t* __restrict__ kidx,
+                                                           const float* __restrict__ kvec, int nk, const float* __restrict__ f,
+                                                           const int32_t* __restrict__ erow, const int32_t* __restrict__ ecol,
+                                                           const float* __restrict__ shift, int E, int n_atoms, int nao,
+                                                           const int32_t* __restrict__ orank, const int32_t* __restrict__ ooff, int accumulate,
+                                                           float* __restrict__ P_on, float* __restrict__ P_off) {
+    __shared__ float part[4][NT * NT][4][64];
+    __shared__ float2 ptab[DR_KCAP];
+    __shared__ int rki[48], rkj[48];                           // rank of orbital a of the row / column atom, or -1
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sl = lane & 15, kq = lane >> 4;
+    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
+    const bool edge = (int)blockIdx.x < E;                     // (block-uniform)
+    int i, j;
+    float* __restrict__ out;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    if (edge) {
+        const int64_t e = blockIdx.x;
+        i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+        out = P_off + e * nao * nao;
+        sx = shift[3 * e], sy = shift[3 * e + 1], sz = shift[3 * e + 2];
+    } else {
+        i = j = (int)blockIdx.x - E;
+        out = P_on + (int64_t)i * nao * nao;
+    }
+    auto phase = [&](int kp) {                                 // |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
+        const double ph = 6.283185307179586 * ((double)kvec[3 * kp] * sx + (double)kvec[3 * kp + 1] * sy + (double)kvec[3 * kp + 2] * sz);
+        double sd, cd;
+        sincos(ph, &sd, &cd);
+        return make_float2((float)cd, (float)sd);
+    };
+    if ((int)threadIdx.x < nao) {
+        const int a = threadIdx.x, ra = orank[(int64_t)i * nao + a], rb = orank[(int64_t)j * nao + a];
+        rki[a] = ra >= 0 && ra < 16 * NT ? ra : -1;
+        rkj[a] = rb >= 0 && rb < 16 * NT ? rb : -1;
+    }
+    if (edge)
+        for (int kp = threadIdx.x; kp < nk && kp < DR_KCAP; kp += 256) ptab[kp] = phase(kp);
+    __syncthreads();
+    int ni = 0, nj = 0;                                        // orbitals the two atoms have: the ranks 0 .. n - 1 of a well-formed table
+    for (int a = 0; a < nao; ++a) ni += rki[a] >= 0, nj += rkj[a] >= 0;
+    const int oi = ooff[i], oj = ooff[j];
+    bool va[NT], vb[NT];
+    int ca[NT], cb[NT];                                        // this lane's columns of C: rank 16 t + sl of the row atom (A operand) and of the column atom (B)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        va[t] = 16 * t + sl < ni, vb[t] = 16 * t + sl < nj;
+        ca[t] = clampi(oi + (va[t] ? 16 * t + sl : 0), M), cb[t] = clampi(oj + (vb[t] ? 16 * t + sl : 0), M);
+    }
+    const int nsteps = (ns + 3) >> 2, chunk = (nsteps + 3) >> 2;
+    const int st0 = wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
+    f32x4 acc[NT][NT];
+#pragma unroll
+    for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+        for (int tb = 0; tb < NT; ++tb) acc[ta][tb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // one step = this lane's state s = 4 st + kq: its weight, its phase and its 2 NT elements of C.  No branch around a load: a slot past ns reads state
+    // ns - 1 with weight 0, a rank past n_i / n_j reads the atom's first orbital and its operand is set to 0.
+    auto load = [&](int st, float& fs, float2& ph, float2 (&xa)[NT], float2 (&xb)[NT]) {
+        const int s_raw = 4 * st + kq, s = s_raw < ns ? s_raw : ns - 1;
+        fs = s_raw < ns ? f[s] : 0.f;
+        const float2* __restrict__ c = Cm + (int64_t)s * M;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) xa[t] = c[ca[t]], xb[t] = c[cb[t]];
+        ph = make_float2(1.f, 0.f);
+        if (edge) {
+            const int kp = clampi(kidx[s], nk);
+            if (kp < DR_KCAP) ph = ptab[kp]; else ph = phase(kp);
+        }
+    };
+    auto step = [&](float fs, float2 ph, const float2 (&xa)[NT], const float2 (&xb)[NT]) {
+        float ax[NT], ay[NT], bx[NT], by[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            ax[t] = va[t] ? fs * xa[t].x : 0.f, ay[t] = va[t] ? fs * xa[t].y : 0.f;
+            const float rx = edge ? fmaf(ph.x, xb[t].x, -(ph.y * xb[t].y)) : xb[t].x;      // exp(i theta) (x + i y); an on-site member has no phase
+            const float ry = edge ? fmaf(ph.y, xb[t].x, ph.x * xb[t].y) : xb[t].y;
+            bx[t] = vb[t] ? rx : 0.f, by[t] = vb[t] ? ry : 0.f;
+        }
+#pragma unroll
+        for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+            for (int tb = 0; tb < NT; ++tb) acc[ta][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ax[ta], bx[tb], acc[ta][tb], 0, 0, 0);
+#pragma unroll
+        for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+            for (int tb = 0; tb < NT; ++tb) acc[ta][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ay[ta], by[tb], acc[ta][tb], 0, 0, 0);
+    };
+    int st = st0;                                              // (wave-uniform bounds: every lane reaches every MFMA)
+    for (; st + 4 <= st1; st += 4) {                           // blocks of 4 steps: all loads of the block are requested before its first MFMA
+        float fs[4];
+        float2 ph[4], xa[4][NT], xb[4][NT];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) load(st + u, fs[u], ph[u], xa[u], xb[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) step(fs[u], ph[u], xa[u], xb[u]);
+    }
+    for (; st < st1; ++st) {
+        float fs;
+        float2 ph, xa[NT], xb[NT];
+        load(st, fs, ph, xa, xb);
+        step(fs, ph, xa, xb);
+    }
+#pragma unroll
+    for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+        for (int tb = 0; tb < NT; ++tb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) part[wave][ta * NT + tb][r][lane] = acc[ta][tb][r];
+    __syncthreads();
+    // C/D map of a 16x16 tile: column = lane & 15, row = 4 (lane >> 4) + r.  Element (a, b) of the row has the ranks (ra, rb): tile (ra >> 4, rb >> 4),
+    // register ra & 3, lane 16 ((ra >> 2) & 3) + (rb & 15); consecutive b of an atom are consecutive lanes.
+    for (int q = threadIdx.x; q < nao * nao; q += 256) {
+        const int a = q / nao, b = q - a * nao, ra = rki[a], rb = rkj[b];
+        if (ra >= 0 && rb >= 0) {
+            const int t = (ra >> 4) * NT + (rb >> 4), r = ra & 3, ln = 16 * ((ra >> 2) & 3) + (rb & 15);
+            const float v = ((part[0][t][r][ln] + part[1][t][r][ln]) + part[2][t][r][ln]) + part[3][t][r][ln];
+            out[q] = accumulate ? out[q] + v : v;
+        } else if (!accumulate) {
+            out[q] = 0.f;
+        }
+    }
+}
+
+extern "C" int hg_density_rows(const float* C, int64_t ns, int M, const int32_t* kidx, const float* kvec, int nk, const float* f, const int32_t* erow,
+                               const int32_t* ecol, const float* shift, int64_t n_edges, int n_atoms, int nao, const int32_t* orank, const int32_t* ooff,
+                               int accumulate, float* P_on, float* P_off, void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (ns < 0) ns = 0;
+    if (M <= 0 || nk <= 0 || n_atoms <= 0 || nao <= 0 || nao > 48 || n_edges < 0 || n_edges + (int64_t)n_atoms > 2147483647LL || ns > 2147483647LL - 16)
+        return hg_fail(-2, "hg_density_rows: bad sizes (M, nk, n_atoms >= 1, 1 <= nao <= 48, n_edges + n_atoms < 2^31, ns < 2^31 - 16)");
+    if (!kvec || !orank || !ooff || !P_on || (ns > 0 && (!C || !kidx || !f)) || (n_edges > 0 && (!erow || !ecol || !shift || !P_off)))
+        return hg_fail(-2, "hg_density_rows: null pointer");
+    if (ns == 0 && accumulate) return 0;                       // nothing to add; without accumulate the launch writes the zero rows
+    const dim3 grid((unsigned)(n_edges + n_atoms));
+#define HG_DENSITY_LAUNCH(NT_)                                                                                                                            \
+    density_rows_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, kidx, kvec, nk, f, erow, ecol, shift, (int)n_edges, n_atoms, \
+                                                                     nao, orank, ooff, accumulate ? 1 : 0, P_on, P_off)
+    if (nao <= 16) HG_DENSITY_LAUNCH(1);
+    else if (nao <= 32) HG_DENSITY_LAUNCH(2);
+    else HG_DENSITY_LAUNCH(3);
+#undef HG_DENSITY_LAUNCH
+    return hg_check_launch("hg_density_rows");
 }

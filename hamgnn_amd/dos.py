@@ -23,7 +23,8 @@ HIP kernel `hg_dos_tetra` (the same GEMM as the broadening with another generato
 tensors, HG_DOS=torch; the baseline of tests/bench_dos_tetra.py).  The formulas and the rule for flat tetrahedra stand in `tetra_dos`'s docstring.
 
 Bond-resolved weights (COOP / COHP / ICOHP: which bonds the states are in) come from hamgnn_amd/bonds.py: `bonds.bond_weights` writes rows in the same
-[ns, Gp] layout from the real-space rows and the eigenvectors, and `broaden`, `tetra_dos` and `tetra_states` take them unchanged.
+[ns, Gp] layout from the real-space rows and the eigenvectors, and `broaden`, `tetra_dos` and `tetra_states` take them unchanged.  The integrated,
+real-space counterpart -- the density matrix on the graph's rows at the occupations of `fermi_level` -- is hamgnn_amd/density.py.
 
 NOT built: the driver from saved Hamiltonian rows (assembly of H(k) / S(k), solver, these steps, per crystal and k-chunk).  Its one run at a realistic size
 (64 Si atoms, M = 832) ended in a GPU launch failure whose cause was not found, so it was taken out with its tests: profiles/dos.md."""

@@ -972,6 +972,63 @@ def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, ep
     return W
 
 
+def density_rows_check(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out, accumulate):
+    """the host checks of density_rows (any device; the torch path of hamgnn_amd/density.py runs them too): dtypes, shapes, devices, the index ranges of kidx /
+    erow / ecol, orank / ooff inside the M columns of C, `out` = (P_on, P_off) where accumulate adds to it; each ValueError names its argument -> (ns, M, N, nao, E, nk)"""
+    if not isinstance(C_, torch.Tensor) or C_.dim() != 2 or C_.dtype != torch.complex64:
+        raise ValueError(f"density_rows: C must be complex64 [ns, M], got {getattr(C_, 'dtype', type(C_).__name__)} {tuple(getattr(C_, 'shape', ()))}")
+    ns, M = int(C_.shape[0]), int(C_.shape[1])
+    if orank.dim() != 2:
+        raise ValueError(f"density_rows: orank must be [N, nao], got {tuple(orank.shape)}")
+    N, nao = int(orank.shape[0]), int(orank.shape[1])
+    E, nk = int(erow.shape[0]) if erow.dim() else -1, int(kvec.shape[0]) if kvec.dim() else -1
+    i32, f32 = torch.int32, torch.float32
+    named = {"kidx": (kidx, (ns,), i32), "kvec": (kvec, (nk, 3), f32), "f": (f, (ns,), f32), "erow": (erow, (E,), i32), "ecol": (ecol, (E,), i32),
+             "shift": (shift, (E, 3), f32), "orank": (orank, (N, nao), i32), "ooff": (ooff, (N,), i32)}
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("density_rows: out must be the pair (P_on, P_off)")
+        named["out[0] (P_on)"], named["out[1] (P_off)"] = (out[0], (N, nao * nao), f32), (out[1], (E, nao * nao), f32)
+    elif accumulate:
+        raise ValueError("density_rows: accumulate needs the out = (P_on, P_off) to add to")
+    for name, (t, shape, dtype) in named.items():
+        if t.dtype != dtype:
+            raise ValueError(f"density_rows: {name} must be {dtype}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"density_rows: {name} must be {list(shape)}, got {list(t.shape)}")
+        if t.device != C_.device:
+            raise ValueError(f"density_rows: {name} is on {t.device}, C on {C_.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"density_rows: {name} must be contiguous")
+    if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
+        raise ValueError(f"density_rows: needs at least one atom, one k-point and one orbital and nao <= 48, got N = {N}, nk = {nk}, M = {M}, nao = {nao}")
+    for name, t, n in (("kidx", kidx, nk), ("erow", erow, N), ("ecol", ecol, N)):      # (a device-to-host copy of two scalars each)
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError(f"density_rows: {name} has entries outside [0, {n})")
+    top = torch.where(orank >= 0, ooff[:, None] + orank, torch.zeros_like(orank))
+    if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
+        raise ValueError(f"density_rows: orank / ooff point outside the {M} compact orbitals of C")
+    return ns, M, N, nao, E, nk
+
+
+@_on_tensor_device
+def density_rows(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out=None, accumulate=False):
+    """(P_on [N, nao^2], P_off [E, nao^2]) fp32 (+)= the density matrix sum_s f[s] Re(phase conj(c_ia) c_jb) sampled on the on-site and edge rows of one crystal
+    from the eigenvector rows C_ [ns, M] complex64 (see include/hamgnn_hip.h:hg_density_rows).  kidx int32 [ns] -> rows of kvec [nk, 3]; f fp32 [ns]; erow /
+    ecol int32 [E], shift [E, 3]; orank int32 [N, nao], ooff int32 [N].  accumulate adds to the given out = (P_on, P_off); otherwise every element is
+    written (into out if given).  All tables are checked here, on the host, before the launch."""
+    _require_gpu(C_)               # (the tables are read below, ahead of the launch)
+    ns, M, N, nao, E, nk = density_rows_check(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out, accumulate)
+    P_on, P_off = out if out is not None else (torch.empty(N, nao * nao, device=C_.device, dtype=torch.float32),
+                                               torch.empty(E, nao * nao, device=C_.device, dtype=torch.float32))
+    if ns == 0 and accumulate:                                 # no state: nothing to add (without accumulate the launch writes the zero rows)
+        return P_on, P_off
+    if not C_.is_contiguous():
+        raise ValueError("density_rows: C must be contiguous")
+    call("hg_density_rows", torch.view_as_real(C_), ns, M, kidx, kvec, nk, f, erow, ecol, shift, E, N, nao, orank, ooff, bool(accumulate), P_on, P_off)
+    return P_on, P_off
+
+
 @_on_tensor_device
 def zero_point_shift(H, Href, S, nao, soc=False, threshold=1e-6):
     """in place on H; returns the shift (device scalar)."""

@@ -491,6 +491,26 @@ int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t* kidx, cons
                     const int32_t* ooff, const int32_t* eptr, const int32_t* eidx, const int32_t* aptr, const int32_t* aidx, int G, int Gp,
                     const float* wk, float* W, void* stream);
 
+/* Density-matrix rows of one crystal (csrc/spectra.hip): the one-particle density matrix sampled where the crystal graph has rows, in the
+ * [n_atoms][nao^2] / [n_edges][nao^2] layout of the rows hg_hk_assemble takes.  C, kidx, kvec, erow, ecol, shift, orank, ooff as hg_bond_weights;
+ * f fp32 [ns]: one real weight per state (k-weight x occupation, times the eigenvalue for the energy-weighted matrix; any sign).
+ *   P_off[e][a][b] (+)= sum_s f[s] Re(exp(2 pi i k_s . shift[e]) conj(C[s][mu(i, a)]) C[s][mu(j, b)]),  i = erow[e], j = ecol[e];
+ *   P_on [i][a][b] (+)= sum_s f[s] Re(conj(C[s][mu(i, a)]) C[s][mu(i, b)]);   exactly 0 where either atom lacks the orbital.
+ * So sum_{a, b} X_off[e][a][b] P_off[e][a][b] = sum_s f[s] t_e(s) with t_e of hg_bond_weights, and (P_on, P_off) is hg_hk_assemble_adjoint of
+ * G_k[p][q] = sum_{s at k} f[s] C[s][p] conj(C[s][q]) without the M x M matrices.
+ * One workgroup per member (edge or atom): an n_i x n_j block with K = the states on v_mfma_f32_16x16x4_f32, tiled over the compact ranks (C is read
+ * contiguously from ooff); the column operand is rotated by the phase once per loaded element (cos / sin per (k-point, member) from a prologue:
+ * k . shift and sincos in double, rounded once; tabulated for the first 1024 k-points, formed per state beyond them), so a tile takes two real
+ * MFMA chains; the 4 waves take contiguous quarters of the 4-state steps and add their tiles as ((w0 + w1) + w2) + w3; the store maps the ranks back
+ * to the nao layout.  No atomics, one summation order: two launches are bit-identical, and a member's block does not depend on the other members.
+ * accumulate 0: every element of P_on and P_off is written (0 at missing orbitals; ns <= 0 gives zero rows); 1: added to what is there (state chunks
+ * in turn, as the solver hands them out), missing-orbital elements left as they are, ns <= 0 returns 0 without a launch.  Table entries are clamped into
+ * range before use; the caller checks them.  No scratch.  Refused (-2): M, nk or n_atoms < 1, nao < 1 or > 48, n_edges < 0, n_edges + n_atoms >= 2^31,
+ * ns > 2^31 - 17, a null pointer where the sizes are not empty.                                                                                */
+int hg_density_rows(const float* C, int64_t ns, int M, const int32_t* kidx, const float* kvec, int nk, const float* f, const int32_t* erow,
+                    const int32_t* ecol, const float* shift, int64_t n_edges, int n_atoms, int nao, const int32_t* orank, const int32_t* ooff,
+                    int accumulate, float* P_on, float* P_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
