@@ -41,14 +41,74 @@ __device__ __forceinline__ float is_mul_bcast(float v, float x, int q) {
 }
 #undef IS_MB_CASE
 
+// The split radial scale of an item's RTM row tiles from one resident set of hidden rows (item_is): S = c0 (W_hi h_hi) + c0 2^-11 (W_hi h_lo + W_lo h_hi),
+// S zero on entry.
+template <int RTM>
+__device__ __forceinline__ void is_radial_split(const f32x4 (&wh)[2][RTM], const f32x4 (&wl)[2][RTM], const IsHidden& hb, f32x4 (&S)[RTM]) {
+    f32x4 S1[RTM];
+#pragma unroll
+    for (int rt = 0; rt < RTM; ++rt) S1[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int rt = 0; rt < RTM; ++rt) S[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh[t][rt]), hb.hi[t], S[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RTM; ++rt) S1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh[t][rt]), hb.lo[t], S1[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RTM; ++rt) S1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wl[t][rt]), hb.hi[t], S1[rt], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const float c0 = hb.c0, c1 = hb.c0 * (1.f / 2048.f);
+#pragma unroll
+    for (int rt = 0; rt < RTM; ++rt) S[rt] = S[rt] * c0 + S1[rt] * c1;
+}
+
+// The 16 edges' hidden rows of one radial MLP (lane (g, el): units 16 G + 4 g .. + 3 of edge el in hv[G]) split into (hi, lo) halves in the K-slot order of the
+// weights' twins, with the TILE's exponent sh (= plan.split_h_exp of the 16 edges' rows): the largest |h| of the wave's 16 x 64 values lands in [2^12, 2^13), as the
+// weights' largest does -- whatever the rows' magnitude, nothing overflows a half and a value is flushed only below 2^-26 of the tile's largest.
+// max |h| of a lane's 16 values in 8 instructions (v_max3_f32 with |.| on its sources: as C++ it was an AND and a MAX per value); a NaN among them is
+// passed over (its edge's column becomes NaN whatever the exponent).  Magnitudes' bit patterns order as integers: the maximum along each DPP row
+// by rotations, of the four rows on the scalar unit -- the same number in every wave of the workgroup, whatever the order they get here in.
+__device__ __forceinline__ void is_split_hidden(const f32x4 (&hv)[4], float s_scale, IsHidden& hb) {
+    float mf = is_absmax3(hv[0][0], hv[0][1], hv[0][2]);
+    mf = is_absmax3(mf, hv[0][3], hv[1][0]);
+    mf = is_absmax3(mf, hv[1][1], hv[1][2]);
+    mf = is_absmax3(mf, hv[1][3], hv[2][0]);
+    mf = is_absmax3(mf, hv[2][1], hv[2][2]);
+    mf = is_absmax3(mf, hv[2][3], hv[3][0]);
+    mf = is_absmax3(mf, hv[3][1], hv[3][2]);
+    mf = is_absmax3(mf, hv[3][3], hv[3][3]);
+    int mb = __builtin_bit_cast(int, mf);
+    { const int o_ = is_dpp_i<0x128>(mb); mb = o_ > mb ? o_ : mb; }       // row_ror:8, 4, 2, 1
+    { const int o_ = is_dpp_i<0x124>(mb); mb = o_ > mb ? o_ : mb; }
+    { const int o_ = is_dpp_i<0x122>(mb); mb = o_ > mb ? o_ : mb; }
+    { const int o_ = is_dpp_i<0x121>(mb); mb = o_ > mb ? o_ : mb; }
+    const int m0 = __builtin_amdgcn_readlane(mb, 0), m1 = __builtin_amdgcn_readlane(mb, 16), m2 = __builtin_amdgcn_readlane(mb, 32), m3 = __builtin_amdgcn_readlane(mb, 48);
+    const int m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3;
+    int sh = (127 + IS_SPLIT_H_TOP) - (((m01 > m23 ? m01 : m23) >> 23) & 0xff);
+    sh = sh < IS_SPLIT_H_MIN ? IS_SPLIT_H_MIN : (sh > IS_SPLIT_H_MAX ? IS_SPLIT_H_MAX : sh);
+    const float hs = __builtin_bit_cast(float, (127 + sh) << 23);
+    hb.c0 = s_scale * __builtin_bit_cast(float, (127 - sh) << 23);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s_ = 0; s_ < 8; ++s_) {
+            const float x = hv[2 * t + (s_ >> 2)][s_ & 3] * hs;
+            const _Float16 h_ = (_Float16)x;
+            hb.hi[t][s_] = h_;
+            hb.lo[t][s_] = (_Float16)((x - (float)h_) * 2048.f);
+        }
+}
+
 // One item on the workgroup's 16 edges.  stage: the phase's staged input block(s), image offset(piece p, row e) = 64 p + 4 e per
 // source (pieces of the FULL irrep block: component a, channel piece s -> p = a * P1 + s).
 // ODD: a super-path with l_i + l_sh + l_k odd (item[7], the reversed-column flag).  Its aligned-frame coupling is antisymmetric in m, so
 // the coefficient of the centre column (m = 0) vanishes for every path of the item (checked by the planner's emulator): the kernel
 // works on the 2 MM remaining columns only -- column slot c < MM is real column c, slot c >= MM is real column c + 1.
-template <int MM, int RTM, bool SPLIT, bool ODD>
+// TWO: the kernel of programs with phases that use both radial generators (tp_is_two_kernel): hbr2 / hbr2_cls are a second resident set (else unused).
+template <int MM, int RTM, bool SPLIT, bool ODD, bool TWO>
 __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict__ Wb, const int* __restrict__ it,
-                                        float* __restrict__ lds, int64_t erow, int lane, const IsHidden& hbr, int hbr_cls HG_PROF_ARG) {
+                                        float* __restrict__ lds, int64_t erow, int lane, const IsHidden& hbr, int hbr_cls, const IsHidden& hbr2, int hbr2_cls HG_PROF_ARG) {
     constexpr int NCR = 2 * MM + 1;                            // real columns (fragment layouts of cf, tile columns)
     constexpr int NC = ODD ? 2 * MM : NCR;                     // column slots this item computes
 #define IS_COL(c) ((ODD && (c) >= MM) ? (c) + 1 : (c))
@@ -88,11 +148,12 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
         const float* __restrict__ hrow = (mlp ? A.h2[1] : A.h2[0]) + erow * A.hidden + 4 * g;
         const f32x4* __restrict__ w3 = reinterpret_cast<const f32x4*>(Wb + it[12]) + lane;
         const int hgrp = A.hidden >> 4;
-        if (mlp == hbr_cls) {
+        if (mlp == hbr_cls || (TWO && mlp == hbr2_cls)) {
             // the 16 edges' hidden rows of the phase's radial MLP (the B operands of these MFMAs, the same for every item of a branch) are
             // resident in registers: read once per phase by the kernel, under the staging -- the planner keeps a phase on one generator where
             // that is free (plan.is_schedule(separate_mlp)); r3 loaded them per item: 4 of an item's ~35 vector loads, and a second round
-            // trip when they missed the L1.
+            // trip when they missed the L1.  A phase whose items use BOTH generators (phase record [5]: the reduced first-layer programs) holds the
+            // other generator's rows as a second set, hbr2, split with its own exponent: the item takes the set of its generator.
             // r6: on the HALF-PRECISION matrix pipe with split operands (plan/program.py: w3_split_fill): x 2^s = hi + 2^-11 lo, hi = f16(x 2^s),
             // lo = f16((x 2^s - hi) 2^11);  S 2^(sw + sh) = W_hi h_hi + 2^-11 (W_hi h_lo + W_lo h_hi) -- 3 MFMAs of K = 32 per half of the 64 hidden units
             // = 6 x 16 pipe cycles per row tile where the fp32 form takes 16 x 32 (27.5 % of the launch's MFMAs), fp32 accumulation in two chains (the
@@ -101,7 +162,7 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
             // magnitude -- no half overflows, a unit is flushed only below 2^-26 of the tile's largest; hbr.c0 = 2^-(sw + sh) undoes both.
             // The weights' split twin follows the fp32 block: [t][rt][hi, lo][lane] float4 = 8 halves in the K-slot order of the resident rows.
             const f32x4* __restrict__ w3s = w3 + 4 * RTM * 64;
-            f32x4 wh[2][RTM], wl[2][RTM], S1[RTM];
+            f32x4 wh[2][RTM], wl[2][RTM];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -109,24 +170,11 @@ __device__ __forceinline__ void item_is(const IsArgs& A, const float* __restrict
                     wh[t][rt] = w3s[((t * RTM + rt) * 2) * 64];
                     wl[t][rt] = w3s[((t * RTM + rt) * 2 + 1) * 64];
                 }
-#pragma unroll
-            for (int rt = 0; rt < RTM; ++rt) S1[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
             // all fragments requested and waited for before the first MFMA: the faster form (6.15 vs 6.55 ms per 131 072 edges, profiles/r06_tp_is.md section 3)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int rt = 0; rt < RTM; ++rt) S[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh[t][rt]), hbr.hi[t], S[rt], 0, 0, 0);
-#pragma unroll
-                for (int rt = 0; rt < RTM; ++rt) S1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh[t][rt]), hbr.lo[t], S1[rt], 0, 0, 0);
-#pragma unroll
-                for (int rt = 0; rt < RTM; ++rt) S1[rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wl[t][rt]), hbr.hi[t], S1[rt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const float c0 = hbr.c0, c1 = hbr.c0 * (1.f / 2048.f);
-#pragma unroll
-            for (int rt = 0; rt < RTM; ++rt) S[rt] = S[rt] * c0 + S1[rt] * c1;
+            if (!TWO || mlp == hbr_cls) is_radial_split<RTM>(wh, wl, hbr, S);      // (a branch, not a select of the operands: 16 registers more per item otherwise)
+            else is_radial_split<RTM>(wh, wl, hbr2, S);
         } else
 #pragma unroll 1
         for (int G0 = 0; G0 < hgrp; G0 += 4) {
@@ -721,25 +769,30 @@ __device__ __forceinline__ void post_is(const IsArgs& A, const float* __restrict
 }
 
 #define IS_CASE(MMv, RTMv) \
-    case (MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, false>(A, g_W, it, lds, erow, lane, hbr, hbr_cls HG_PROF_PASS); break;
+    case (MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, false, TWO>(A, g_W, it, lds, erow, lane, hbr, hbr_cls, hbr2, hbr2_cls HG_PROF_PASS); break;
 #define IS_CASE_ODD(MMv, RTMv) \
-    case (64 + MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, true>(A, g_W, it, lds, erow, lane, hbr, hbr_cls HG_PROF_PASS); break;
+    case (64 + MMv * 8 + RTMv): item_is<MMv, RTMv, SPLIT, true, TWO>(A, g_W, it, lds, erow, lane, hbr, hbr_cls, hbr2, hbr2_cls HG_PROF_PASS); break;
 
 // A launch runs `nparts` sub-schedules (blockIdx.y) of the same program: every part owns a disjoint set of output segments and the
 // phases / groups / items that feed them (plan.py:is_schedule(parts=...)).  One part = the whole program (large edge counts); several
 // parts spread ONE 16-edge tile's serial 34 k-MFMA pass over several workgroups when there are fewer tiles than CUs (small crystals).
 // part record, int32[16]: {first segment, segments, first phase, phases, trash_off, stage_off, ctr_off (float offsets in the LDS),
-// copy_stride, rowtab_off, rowtab_begin, rowtab_len, lite, 0, 0, 0, 0}.  copy_stride > 0: each of the four waves accumulates
+// copy_stride, rowtab_off, rowtab_begin, rowtab_len, lite, W3 split twins, their exponent, a phase uses both generators (-> tp_is_two_kernel), 0}.  copy_stride > 0: each of the four waves accumulates
 // into its own copy of the part's tiles (copy w at + w * copy_stride), so all waves can work on one output segment at once; the copies are
 // summed before the epilogue.  r5: several parts may share a segment range and split its PHASES (plan.is_schedule ("2d", P, K); replayed hipGraphs only):
 // their segments are flagged SEG_ATOMIC, the epilogues add into zero-filled rows.
 #define IS_PART_I32 16
 
-template <bool SPLIT, bool LITE>
-__global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE : IS_NW) / 2) void tp_is_kernel(const IsArgs A0, const int* __restrict__ g_segs, const int* __restrict__ g_blocks,
-                                                       const int* __restrict__ g_phases, const int* __restrict__ g_groups,
-                                                       const int* __restrict__ g_items, const float* __restrict__ g_W,
-                                                       const int* __restrict__ g_parts, const int* __restrict__ g_rowtab) {
+// The kernel's body.  TWO = false: tp_is_kernel<SPLIT, LITE>; TWO = true: tp_is_two_kernel<SPLIT>, the launch of programs that have a phase whose items use both
+// radial generators (part record [14]; the reduced first-layer programs), which keeps a second set of hidden rows resident in such phases.  A kernel of its own
+// because the 17 registers of the second set, held across every item, cost the launches that never use them 0.4 ms each on the benchmark (1 %): the complete
+// programs keep the kernel they had (profiles/dense_epilogue_two_generators.md).
+template <bool SPLIT, bool LITE, bool TWO>
+__device__ __forceinline__ void tp_is_body(const IsArgs& A0, const int* __restrict__ g_segs, const int* __restrict__ g_blocks,
+                                           const int* __restrict__ g_phases, const int* __restrict__ g_groups,
+                                           const int* __restrict__ g_items, const float* __restrict__ g_W,
+                                           const int* __restrict__ g_parts, const int* __restrict__ g_rowtab) {
+    static_assert(!(TWO && LITE), "lite programs have no resident hidden rows");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NW = LITE ? IS_NW_LITE : IS_NW, NT = 64 * NW; // lite programs: 8 waves on the tile (four per SIMD at <= 128 VGPRs; the default
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63; // instantiation needs 219)
@@ -790,11 +843,21 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
         // the hidden rows of the phase's radial MLP (P[4]; -1: none / hidden width != 64), resident for its items (item_is): requested here,
         // first used -- split into halves -- after the staging, whose wait covers them, while the wave would wait for the others' staging
         const int hbr_cls = (A.hidden == 64 && A.s_split && (P[4] == 0 || (P[4] == 1 && A.h2[1]))) ? P[4] : -1;
-        f32x4 hv[4];                                           // (16 registers under the staging, as many as the halves they become)
+        // P[5]: the phase's tensor-product items use BOTH generators (plan/schedule_is.py; the reduced first-layer programs): the other generator's rows are
+        // requested next to the first's and kept as a second set, so its items take the half-precision form as well.  Unmarked phases load and convert nothing more.
+        const int hbr2_cls = (TWO && hbr_cls >= 0 && P[5] == 1 && A.h2[0] && A.h2[1]) ? 1 - hbr_cls : -1;
+        f32x4 hv[4], hv2[4];                                   // (16 registers under the staging, as many as the halves they become)
         {
             const float* __restrict__ hrow = (hbr_cls == 1 ? A.h2[1] : A.h2[0]) + erow * A.hidden + 4 * g;
 #pragma unroll
             for (int G = 0; G < 4; ++G) hv[G] = hbr_cls >= 0 ? *reinterpret_cast<const f32x4*>(hrow + 16 * G) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        if constexpr (TWO) {
+            if (hbr2_cls >= 0) {
+                const float* __restrict__ hrow = (hbr2_cls == 1 ? A.h2[1] : A.h2[0]) + erow * A.hidden + 4 * g;
+#pragma unroll
+                for (int G = 0; G < 4; ++G) hv2[G] = *reinterpret_cast<const f32x4*>(hrow + 16 * G);
+            }
         }
         __syncthreads();                                       // every wave is done with the previous blocks (and the zero fill)
         HG_T(5);                                               // waiting for the slowest wave of the previous phase
@@ -817,41 +880,16 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
 #endif
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        IsHidden hbr;                                          // split into (hi, lo) halves once per phase, in the K-slot order of the weights' twins
-        {
-            // the TILE's exponent sh (= plan.split_h_exp of the 16 edges' rows): the largest |h| of the wave's 16 x 64 values lands in [2^12, 2^13), as the
-            // weights' largest does -- whatever the rows' magnitude, nothing overflows a half and a value is flushed only below 2^-26 of the tile's largest.
-            // max |h| of a lane's 16 values in 8 instructions (v_max3_f32 with |.| on its sources: as C++ it was an AND and a MAX per value); a NaN among them is
-            // passed over (its edge's column becomes NaN whatever the exponent).  Magnitudes' bit patterns order as integers: the maximum along each DPP row
-            // by rotations, of the four rows on the scalar unit -- the same number in every wave of the workgroup, whatever the order they get here in.
-            float mf = is_absmax3(hv[0][0], hv[0][1], hv[0][2]);
-            mf = is_absmax3(mf, hv[0][3], hv[1][0]);
-            mf = is_absmax3(mf, hv[1][1], hv[1][2]);
-            mf = is_absmax3(mf, hv[1][3], hv[2][0]);
-            mf = is_absmax3(mf, hv[2][1], hv[2][2]);
-            mf = is_absmax3(mf, hv[2][3], hv[3][0]);
-            mf = is_absmax3(mf, hv[3][1], hv[3][2]);
-            mf = is_absmax3(mf, hv[3][3], hv[3][3]);
-            int mb = __builtin_bit_cast(int, mf);
-            { const int o_ = is_dpp_i<0x128>(mb); mb = o_ > mb ? o_ : mb; }       // row_ror:8, 4, 2, 1
-            { const int o_ = is_dpp_i<0x124>(mb); mb = o_ > mb ? o_ : mb; }
-            { const int o_ = is_dpp_i<0x122>(mb); mb = o_ > mb ? o_ : mb; }
-            { const int o_ = is_dpp_i<0x121>(mb); mb = o_ > mb ? o_ : mb; }
-            const int m0 = __builtin_amdgcn_readlane(mb, 0), m1 = __builtin_amdgcn_readlane(mb, 16), m2 = __builtin_amdgcn_readlane(mb, 32), m3 = __builtin_amdgcn_readlane(mb, 48);
-            const int m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3;
-            int sh = (127 + IS_SPLIT_H_TOP) - (((m01 > m23 ? m01 : m23) >> 23) & 0xff);
-            sh = sh < IS_SPLIT_H_MIN ? IS_SPLIT_H_MIN : (sh > IS_SPLIT_H_MAX ? IS_SPLIT_H_MAX : sh);
-            const float hs = __builtin_bit_cast(float, (127 + sh) << 23);
-            hbr.c0 = A.s_scale * __builtin_bit_cast(float, (127 - sh) << 23);
+        IsHidden hbr, hbr2;                                    // split into (hi, lo) halves once per phase, each set with the exponent of its own rows (is_split_hidden)
+        is_split_hidden(hv, A.s_scale, hbr);
+        if constexpr (TWO) {                                   // (TWO = false: hbr2 is never read)
+            if (hbr2_cls >= 0) {
+                is_split_hidden(hv2, A.s_scale, hbr2);
+            } else {
+                hbr2.c0 = 0.f;
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int s_ = 0; s_ < 8; ++s_) {
-                    const float x = hv[2 * t + (s_ >> 2)][s_ & 3] * hs;
-                    const _Float16 h_ = (_Float16)x;
-                    hbr.hi[t][s_] = h_;
-                    hbr.lo[t][s_] = (_Float16)((x - (float)h_) * 2048.f);
-                }
+                for (int t = 0; t < 2; ++t) hbr2.hi[t] = hbr2.lo[t] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            }
         }
         __builtin_amdgcn_sched_barrier(0);                     // (the split stays on this side of the barrier: in the wait for the other waves' staging)
         __syncthreads();
@@ -978,6 +1016,22 @@ __global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE 
 #endif
 }
 
+template <bool SPLIT, bool LITE>
+__global__ __launch_bounds__(LITE ? 64 * IS_NW_LITE : IS_NT, (LITE ? IS_NW_LITE : IS_NW) / 2) void tp_is_kernel(const IsArgs A0, const int* __restrict__ g_segs, const int* __restrict__ g_blocks,
+                                                       const int* __restrict__ g_phases, const int* __restrict__ g_groups,
+                                                       const int* __restrict__ g_items, const float* __restrict__ g_W,
+                                                       const int* __restrict__ g_parts, const int* __restrict__ g_rowtab) {
+    tp_is_body<SPLIT, LITE, false>(A0, g_segs, g_blocks, g_phases, g_groups, g_items, g_W, g_parts, g_rowtab);
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(IS_NT, IS_NW / 2) void tp_is_two_kernel(const IsArgs A0, const int* __restrict__ g_segs, const int* __restrict__ g_blocks,
+                                                                      const int* __restrict__ g_phases, const int* __restrict__ g_groups,
+                                                                      const int* __restrict__ g_items, const float* __restrict__ g_W,
+                                                                      const int* __restrict__ g_parts, const int* __restrict__ g_rowtab) {
+    tp_is_body<SPLIT, false, true>(A0, g_segs, g_blocks, g_phases, g_groups, g_items, g_W, g_parts, g_rowtab);
+}
+
 #ifdef HG_PROF
 extern "C" int hg_prof_is_read(unsigned long long* out16, int reset) {
     hipDeviceSynchronize();
@@ -1046,22 +1100,29 @@ extern "C" int hg_tp_is(const float* const* src, const int64_t* src_stride, int 
     A.run_id = run_id;
     if (run_id && nparts != 1) return hg_fail(-2, "hg_tp_is: the fused scatter needs a single-part launch");
     if (rot_mask && !wig) return hg_fail(-2, "hg_tp_is: rotated sources need the Wigner rows");
-    static unsigned char lds_attr_done[4][HG_MAX_DEVICES];     // once per device (not a stream operation: illegal during graph capture)
+    static unsigned char lds_attr_done[6][HG_MAX_DEVICES];     // once per device (not a stream operation: illegal during graph capture)
+    if (int rc = hg_lds_attr_once(lds_attr_done[4], dev_guard.dev, (const void*)tp_is_two_kernel<false>, 160 * 1024)) return rc;
+    if (int rc = hg_lds_attr_once(lds_attr_done[5], dev_guard.dev, (const void*)tp_is_two_kernel<true>, 160 * 1024)) return rc;
     if (int rc = hg_lds_attr_once(lds_attr_done[0], dev_guard.dev, (const void*)tp_is_kernel<false, false>, 160 * 1024)) return rc;
     if (int rc = hg_lds_attr_once(lds_attr_done[1], dev_guard.dev, (const void*)tp_is_kernel<true, false>, 160 * 1024)) return rc;
     if (int rc = hg_lds_attr_once(lds_attr_done[2], dev_guard.dev, (const void*)tp_is_kernel<false, true>, 160 * 1024)) return rc;
     if (int rc = hg_lds_attr_once(lds_attr_done[3], dev_guard.dev, (const void*)tp_is_kernel<true, true>, 160 * 1024)) return rc;
     const unsigned grid = (unsigned)((rows + 15) / 16);
     const bool lite = p0[11] != 0;                             // part record [11]: the program holds lite_mode items (plan.is_schedule)
-#define IS_LAUNCH(SPLITv, LITEv, GRID) \
-    hipLaunchKernelGGL((tp_is_kernel<SPLITv, LITEv>), GRID, dim3(LITEv ? 64 * IS_NW_LITE : IS_NT), lds_bytes, (hipStream_t)stream, A, seg_table, block_table, phase_table, \
+    // part record [14]: some phase of the program uses both radial generators -- where the kernel can hold both sets of hidden rows (the conditions of the
+    // resident rows, tp_is_body) the launch takes the kernel that does; every other program keeps tp_is_kernel
+    const bool two = !lite && p0[14] == 1 && A.s_split && h2_node && h2_edge;
+#define IS_LAUNCH(KERNEL, LITEv, GRID) \
+    hipLaunchKernelGGL((KERNEL), GRID, dim3(LITEv ? 64 * IS_NW_LITE : IS_NT), lds_bytes, (hipStream_t)stream, A, seg_table, block_table, phase_table, \
                        group_table, item_table, weights, part_table, row_table)
     if (nparts == 1) {
-        if (lite) IS_LAUNCH(false, true, dim3(grid));
-        else IS_LAUNCH(false, false, dim3(grid));
+        if (lite) IS_LAUNCH((tp_is_kernel<false, true>), true, dim3(grid));
+        else if (two) IS_LAUNCH(tp_is_two_kernel<false>, false, dim3(grid));
+        else IS_LAUNCH((tp_is_kernel<false, false>), false, dim3(grid));
     } else {
-        if (lite) IS_LAUNCH(true, true, dim3(grid, (unsigned)nparts));
-        else IS_LAUNCH(true, false, dim3(grid, (unsigned)nparts));
+        if (lite) IS_LAUNCH((tp_is_kernel<true, true>), true, dim3(grid, (unsigned)nparts));
+        else if (two) IS_LAUNCH(tp_is_two_kernel<true>, false, dim3(grid, (unsigned)nparts));
+        else IS_LAUNCH((tp_is_kernel<true, false>), false, dim3(grid, (unsigned)nparts));
     }
 #undef IS_LAUNCH
     return hg_check_launch("hg_tp_is");

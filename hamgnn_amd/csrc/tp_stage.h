@@ -3,6 +3,7 @@
 // Hand-written HIP for gfx950 (CDNA4).
 #pragma once
 #include "hg_device.h"
+#include "tp_epilogue_map.h"
 
 // the 16 edges' hidden rows of a phase's radial MLP as B operands of v_mfma_f32_16x16x32_f16: x = hi + lo (csrc/tp_is.hip, plan/program.py:w3_split_fill)
 // c0 = 2^-(sw + sh): undoes the weights' exponent and the tile's
@@ -113,12 +114,12 @@ __device__ __forceinline__ void epilogue_is(const IsArgs& A, const float* __rest
     if (red) valid = sc.last && sc.row >= 0;
     float* __restrict__ ob = A.out + (red ? (int64_t)(sc.row >= 0 ? sc.row : 0) : e) * A.ostride + out_off;
     const int wend = mul_k + ((flags >> 8) & 0xff);            // + channel-padding slots of the planar block (last chunk only)
-    // work unit = (output component a, 16 consecutive channels): one wave writes 64 contiguous bytes per edge and component in four
-    // back-to-back stores, so the memory side sees whole sectors (interleaving the channels of one component over the waves
-    // tripled the HBM write traffic: WRITE_SIZE 1.39 GB vs 0.46 GB of output per 131 072 edges)
-    const int nw16 = (wend + 15) >> 4;
-    const int U = NCO * nw16, per = (U + NW - 1) / NW;              // each wave takes a contiguous range of units (adjacent bytes of the row)
-    const int u_begin = wave * per, u_end = (u_begin + per) < U ? (u_begin + per) : U;
+    // work unit = one float4 of the segment's planar block, unit j = a * nq + quad (tp_epilogue_map.h): a wave step serves four consecutive units,
+    // one per lane group, and a wave a contiguous range of steps -- 64 contiguous bytes per edge and wave instruction where the components
+    // follow each other without a gap, so the memory side sees whole sectors (interleaving the channels of one component over the waves
+    // tripled the HBM write traffic: WRITE_SIZE 1.39 GB vs 0.46 GB of output per 131 072 edges).  Units of 16 channels per component
+    // left the lane groups beyond a narrow segment's channels idle: 106 wave steps per tile of the set-A blocks where these take 65.
+    const IsEpiMap em = is_epi_map(NCO, wend, NW, wave);
     // a lane owns FOUR consecutive channels of one (edge, component): 4 NCO tile reads in flight, one 16-byte store -- a wave writes 16 edges x
     // 64 contiguous bytes per request (r3: a dword per lane, four requests for the same bytes)
     if (LK > 0 && (flags & SEG_UNROTATE) && (flags & SEG_CENTRE)) {
@@ -128,9 +129,9 @@ __device__ __forceinline__ void epilogue_is(const IsArgs& A, const float* __rest
         const float* __restrict__ dl = dstage + el;
         const float* __restrict__ tc = tl + LK * 16;
 #pragma unroll 1
-        for (int u = u_begin; u < u_end; ++u) {
-            const int a = u / nw16, w = (u - a * nw16) * 16 + 4 * g;
-            if (w >= wend) continue;
+        for (int s = em.s_begin; s < em.s_end; ++s) {
+            int a, w;
+            if (!is_epi_unit(em, s, g, a, w)) continue;
             const float dc = dl[a * 16];
             f32x4 acc;
 #pragma unroll
@@ -144,9 +145,9 @@ __device__ __forceinline__ void epilogue_is(const IsArgs& A, const float* __rest
     } else if (flags & SEG_UNROTATE) {
         const float* __restrict__ dl = dstage + el;
 #pragma unroll 1
-        for (int u = u_begin; u < u_end; ++u) {
-            const int a = u / nw16, w = (u - a * nw16) * 16 + 4 * g;
-            if (w >= wend) continue;
+        for (int s = em.s_begin; s < em.s_end; ++s) {
+            int a, w;
+            if (!is_epi_unit(em, s, g, a, w)) continue;
             float dc[NCO];
 #pragma unroll
             for (int m = 0; m < NCO; ++m) dc[m] = dl[(m * NCO + a) * 16];
@@ -166,9 +167,9 @@ __device__ __forceinline__ void epilogue_is(const IsArgs& A, const float* __rest
         }
     } else {
 #pragma unroll 1
-        for (int u = u_begin; u < u_end; ++u) {
-            const int a = u / nw16, w = (u - a * nw16) * 16 + 4 * g;
-            if (w >= wend) continue;
+        for (int s = em.s_begin; s < em.s_end; ++s) {
+            int a, w;
+            if (!is_epi_unit(em, s, g, a, w)) continue;
             f32x4 acc;
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = w + k < mul_k ? tl[(w + k) * rowstride + a * 16] : 0.f;

@@ -14,7 +14,8 @@ from .layout import ITEM_I32, IT_LIN, IT_LINC, IT_LINM, IT_POST, IT_STREAM, IT_T
 IS_WAVES = int(os.environ.get("HG_IS_WAVES", "4"))      # waves of a workgroup (= IS_NW of csrc/tp_is.hip); all on the same 16 edges
 IS_WAVES_LITE = int(os.environ.get("HG_LITE_WAVES", "8"))   # ... of the lite_mode instantiation (= IS_NW_LITE: four waves per SIMD at <= 128 VGPRs)
 IS_BLOCK_I32 = 8                   # {s0, s1, in_off, in_mulp, li, nsrc, stage_off0, stage_off1}
-IS_PHASE_I32 = 8                   # {block_begin, block_end, group_begin, group_end, radial generator whose hidden rows the kernel keeps resident (-1: none), 0..}
+IS_PHASE_I32 = 8                   # {block_begin, block_end, group_begin, group_end, radial generator whose hidden rows the kernel keeps resident (-1: none),
+#                                    1: its tensor-product items use BOTH generators (the kernel keeps the other one's rows resident too), 0, 0}
 IS_LDS_BYTES = 80 * 1024           # two workgroups per CU
 IS_ITEM_I32 = 24                   # item record of the IS kernel = fused-kernel record + {lk, mul_k, rto, tile_off} of its segment
 
@@ -23,13 +24,16 @@ IS_ITEM_I32 = 24                   # item record of the IS kernel = fused-kernel
 class IsSchedule:
     seg_table: np.ndarray          # int32[nseg][8] = {lk, mul_k, rto, out_off, out_mulp, tile_off, wigner stage_off, flags | batch bit}
     block_table: np.ndarray        # int32[nblock][8]: input irrep blocks; stage offsets in floats relative to the staging area
-    phase_table: np.ndarray        # int32[nphase][4]: the blocks staged together and the work groups that read them
+    phase_table: np.ndarray        # int32[nphase][8]: [0:4] the blocks staged together and the work groups that read them; [4] the radial generator whose
+    #                                hidden rows the kernel keeps resident in the phase (-1: none); [5] = 1: the phase's tensor-product items use both
+    #                                generators, the kernel keeps the second one's rows resident next to the first's; [6], [7] unused
     group_table: np.ndarray        # int32[ngroup][2] = {item_begin, item_end}: all items of one (phase, output segment); claimed
     #                                dynamically by the waves (largest first), so no two waves update one tile between barriers
     item_table: np.ndarray         # int32[nitems][24]: Program.item_table records with [1], [2] = stage offsets of source 0 / 1 (-1),
     #                                [20..23] = {lk, mul_k, rto, tile_off} of the item's segment
     part_table: np.ndarray         # int32[nparts][16] = {seg_begin, nseg, phase_begin, nphase, trash_off, stage_off, ctr_off, copy_stride,
-    #                                rowtab_off (LDS float offset of the part's row table), rowtab_begin, rowtab_len, lite flag, W3 split twins (0 / 1), their exponent sw, 0, 0}
+    #                                rowtab_off (LDS float offset of the part's row table), rowtab_begin, rowtab_len, lite flag, W3 split twins (0 / 1), their exponent sw,
+    #                                1 if a phase of the program uses both radial generators (phase_table [5]), 0}
     #                                copy_stride > 0: every wave owns a private copy of the part's tiles (floats between copies)
     rowtab: np.ndarray             # int32: per part, for every (segment, row tile, row) of GEMM2's output the LDS float offset of that
     #                                row's CENTRE column (m = 0) inside its segment tile; rows beyond mul_k -> the shared trash row.
@@ -60,7 +64,8 @@ class IsSchedule:
 
 
 SEG_NEWBATCH = 1 << 16             # IS epilogue: this segment starts a new Wigner staging batch
-IS_PART_I32 = 16                   # [12] = 1: the program's W3 blocks are followed by their split-half-precision twins, scaled by 2^[13] (plan/program.py:w3_split_fill); [14], [15] unused
+IS_PART_I32 = 16                   # [12] = 1: the program's W3 blocks are followed by their split-half-precision twins, scaled by 2^[13] (plan/program.py:w3_split_fill); [14] = 1: some phase of the program is flagged [5]
+#                                    (both generators: the launch takes tp_is_two_kernel, csrc/tp_is.hip); [15] unused
 
 
 def _item_rto(rec, segs, vsegs=()):
@@ -233,6 +238,9 @@ def is_schedule(prog: "Program", parts=1, separate_mlp: Optional[bool] = None) -
         worst_balance = min(worst_balance, sub["balance"])
         part_cost.append(sub["crit"])
     items = np.asarray(items_all, np.int32).reshape(-1, IS_ITEM_I32)
+    both_any = int(any(int(p[5]) for p in ptab))               # part record [14]: the launch takes the kernel that can hold both generators' hidden rows
+    for rec in parttab:
+        rec[14] = both_any
     return IsSchedule(np.asarray(segs_all, np.int32).reshape(-1, SEG_I32), np.asarray(btab, np.int32).reshape(-1, IS_BLOCK_I32),
                       np.asarray(ptab, np.int32).reshape(-1, IS_PHASE_I32), np.asarray(gtab, np.int32).reshape(-1, 2), items,
                       np.ascontiguousarray(np.asarray(parttab, np.int32).reshape(-1, IS_PART_I32)), np.asarray(rowtab_all, np.int32),
@@ -519,7 +527,9 @@ def _is_schedule_part(prog: "Program", members: List[int], hp4: int, seg_base: i
         # the generator whose hidden rows stay in registers during the phase: the one that carries most of its tensor-product work
         w = [sum(_item_cost(r, prog.seg_table, hp4, prog.vsegs) for recs in units for r in recs if int(r[0]) == IT_TP and int(r[10]) == c) for c in (0, 1)]
         res_cls = -1 if not any(w) else int(w[1] > w[0])
-        ptab.append([block_base + b0, block_base + len(btab), group_base + g0, group_base + len(gtab), res_cls, 0, 0, 0])
+        # [5]: the phase's tensor-product items use BOTH generators -- the kernel then keeps the other one's hidden rows resident as well (csrc/tp_is.hip)
+        both = int(all(any(int(r[0]) == IT_TP and int(r[10]) == c for recs in units for r in recs) for c in (0, 1)))
+        ptab.append([block_base + b0, block_base + len(btab), group_base + g0, group_base + len(gtab), res_cls, both, 0, 0])
         phase_cls.append(_cls(ph) or 0)
     if post_items:                                             # the last phase: nothing staged, one work group per segment's post-op, dearest first
         g0 = len(gtab)

@@ -112,7 +112,8 @@ int hg_tp_fused(const float* const* src, const int64_t* src_stride, int nsrc, co
  *   seg_table   int32[nseg][8]   = {lk, mul_k, rto, out_off, out_mulp, tile_off, Wigner stage_off, flags (| 1<<16: new batch)}
  *   block_table int32[nblock][8] = {s0, s1, in_off, in_mulp, li, nsrc, stage_off0, stage_off1}
  *   phase_table int32[nphase][8] = {block_begin, block_end, group_begin, group_end, radial generator (0 / 1) whose hidden rows the kernel
- *               keeps in registers for the phase's items or -1, 0, 0, 0};  group_table int32[ngroup][2] = item range
+ *               keeps in registers for the phase's items or -1, 1 when the phase's tensor-product items use BOTH generators (the kernel then
+ *               keeps the other generator's rows in registers as well) else 0, 0, 0};  group_table int32[ngroup][2] = item range
  *   item_table  int32[nitems][24]: as for hg_tp_fused with [1], [2] = stage offsets of source 0 / 1 (-1), [19] = segment,
  *               [20..22] = {lk, mul_k, rto} of that segment, [23] = first row-table entry of the rows its GEMM2 writes
  *   row_table   int32: per part, for every output row (segment, 16-row tile, row) of GEMM2 the LDS float offset (relative to a tile
@@ -120,7 +121,8 @@ int hg_tp_fused(const float* const* src, const int64_t* src_stride, int nsrc, co
  *   part_table  int32[nparts][16] = {first segment, segments, first phase, phases, trash_off, stage_off, ctr_off, copy_stride,
  *               rowtab_off (LDS float offset of the part's copy of the row table), rowtab_begin, rowtab_len, lite flag, [12] W3 split twins present (1: the
  *               W3 blocks of `weights` are followed by the split-half-precision twins hg_w3_split_refill writes, and hg_tp_is forms the radial scale from them
- *               when hidden == 64; 0: the fp32 form), [13] the twins' exponent (they hold w * 2^[13]), 0, 0}: the launch runs
+ *               when hidden == 64; 0: the fp32 form), [13] the twins' exponent (they hold w * 2^[13]), [14] 1 when a phase of the
+ *               program is marked phase_table[.][5] (the launch then takes the kernel that holds both generators' hidden rows; read from part 0), 0}: the launch runs
  *               nparts sub-schedules (grid.y) that own disjoint sets of output segments; one part = the whole program, several
  *               parts spread a 16-edge tile's serial pass over several workgroups when there are fewer tiles than CUs (small
  *               crystals: BASELINE configs #1 and #5).  trash_off / stage_off / ctr_off: float offsets of the padding-row sink,
