@@ -3,7 +3,7 @@ from the real-space rows the head emits -- which bonds the states are in, and wh
 it takes the solver's eigenvectors and hands dos.py's kernels their weight rows.
 
     groups = bond_groups(edge_index, cell_shift, z, by="pair")              # host: which edges / atoms make up a bond (CSR lists + labels)
-    tables = bond_tables(head, z, edge_index, cell_shift, device)           # device: row / column atom and shift per edge, orank, ooff, M
+    tables = bond_tables(head, z, edge_index, cell_shift, device)           # device: kspace.CrystalTables (row / column atom and shift per edge, orank, ooff, M)
     Gp = dos.padded_groups(len(groups[4]))
     W_S = bond_weights(C, kidx, kvec, Son, Soff, tables, groups, wk, Gp)    # overlap rows: COOP weights
     W_H = bond_weights(C, kidx, kvec, Hon, Hoff, tables, groups, wk, Gp)    # Hamiltonian rows: COHP weights
@@ -32,6 +32,8 @@ import numpy as np
 import torch
 
 from . import dos, ops
+from .basis import orbital_rank_table
+from .kspace import CrystalTables
 
 BY = ("edge", "pair", "species_pair")
 
@@ -119,29 +121,20 @@ def bond_groups(edge_index, nbr_shift, z, by="pair", onsite=True, pos=None, cell
 
 # ------------------------------------------------------------------------------------------------ device tables
 def bond_tables(head, z, edge_index, nbr_shift, device):
-    """The tables hg_bond_weights reads for one crystal, on `device`: {"erow", "ecol" int32 [E] (row / column atom of every edge: edge_index[0] / [1], as
-    kspace._pair_tables reads them), "shift" fp32 [E, 3], "orank" int32 [N, nao] (rank of an orbital inside its element's valid set or -1, the head's basis
-    table as HamGNNPlusPlusOut.compile builds it), "ooff" int32 [N] (first compact index of every atom, as kspace._compact_index), "M", "nao"}."""
+    """The kspace.CrystalTables of one crystal on `device`, as hg_bond_weights and hg_density_rows read them: erow / ecol = edge_index[0] / [1], orank from the
+    head's basis (basis.orbital_rank_table, the table HamGNNPlusPlusOut.compile uploads; the head need not be compiled), ooff, M, and `nbr_shift` as given --
+    integer cell shifts for reduced k-points, or the Cartesian pair of the assembly."""
     zs = _np(z, np.int64).reshape(-1)
-    nao = int(head.nao_max)
-    by_z = np.full((119, nao), -1, dtype=np.int32)
-    for Z, orb in head.basis_def.items():
-        by_z[Z, sorted(orb)] = np.arange(len(orb), dtype=np.int32)
     missing = sorted({int(Z) for Z in zs if int(Z) not in head.basis_def})
     if missing:
         raise ValueError(f"bond_tables: the head's basis has no element {missing}")
-    orank = by_z[zs]
-    norb = (orank >= 0).sum(1)
-    ooff = (np.cumsum(norb) - norb).astype(np.int32)
     ei = _np(edge_index, np.int64)
     if ei.ndim != 2 or ei.shape[0] != 2 or (ei.size and (ei.min() < 0 or ei.max() >= len(zs))):
         raise ValueError(f"bond_tables: edge_index must be [2, E] with entries in [0, {len(zs)}), got {ei.shape}")
     sh = _np(nbr_shift, np.float32).reshape(-1, 3)
     if sh.shape[0] != ei.shape[1]:
         raise ValueError(f"bond_tables: nbr_shift must be [{ei.shape[1]}, 3], got {sh.shape}")
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    return {"erow": dev(ei[0].astype(np.int32)), "ecol": dev(ei[1].astype(np.int32)), "shift": dev(sh), "orank": dev(orank), "ooff": dev(ooff),
-            "M": int(norb.sum()), "nao": nao}
+    return CrystalTables.from_edges(ei, sh, zs, orbital_rank_table(head.basis_def, int(head.nao_max)), device)
 
 
 # ------------------------------------------------------------------------------------------------ the weights: HIP kernel or torch
@@ -189,9 +182,9 @@ def bond_weights(C, kidx, kvec, X_on, X_off, tables, groups, wk, Gp):
     eptr, eidx, aptr, aidx = (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, dtype=np.int32)).to(C.device)
                               for g in groups[:4])
     t = tables
-    if int(C.shape[1]) != t["M"]:
-        raise ValueError(f"bond_weights: C has {int(C.shape[1])} orbital columns, the tables {t['M']}")
-    args = (C, kidx, kvec, X_on, X_off, t["erow"], t["ecol"], t["shift"], t["orank"], t["ooff"], eptr, eidx, aptr, aidx, wk, int(Gp))
+    if int(C.shape[1]) != t.M:
+        raise ValueError(f"bond_weights: C has {int(C.shape[1])} orbital columns, the tables {t.M}")
+    args = (C, kidx, kvec, X_on, X_off, t.erow, t.ecol, t.shift, t.orank, t.ooff, eptr, eidx, aptr, aidx, wk, int(Gp))
     if dos._use_kernels(C):
         return ops.bond_weights(*args)
     if int(Gp) < int(eptr.shape[0]):

@@ -92,9 +92,9 @@ def density_rows(C, kidx, kvec, f, tables, out=None, accumulate=False):
     cover its own states only.  Every argument is checked on the host before anything runs (ValueError naming it).  HIP kernel hg_density_rows, or torch ops
     (see dos._use_kernels)."""
     t = tables
-    if isinstance(C, torch.Tensor) and C.dim() == 2 and int(C.shape[1]) != t["M"]:
-        raise ValueError(f"density_rows: C has {int(C.shape[1])} orbital columns, the tables {t['M']}")
-    args = (C, kidx, kvec, f, t["erow"], t["ecol"], t["shift"], t["orank"], t["ooff"])
+    if isinstance(C, torch.Tensor) and C.dim() == 2 and int(C.shape[1]) != t.M:
+        raise ValueError(f"density_rows: C has {int(C.shape[1])} orbital columns, the tables {t.M}")
+    args = (C, kidx, kvec, f, t.erow, t.ecol, t.shift, t.orank, t.ooff)
     if isinstance(C, torch.Tensor) and dos._use_kernels(C):
         return ops.density_rows(*args, out=out, accumulate=accumulate)
     ops.density_rows_check(*args, out, accumulate)
@@ -113,15 +113,15 @@ def populations(P_on, P_off, X_on, X_off, tables):
     """(per_atom [N], per_orbital [N, nao]): gross populations on the row atom, per_orbital[i, a] = sum_b P_on[i][a, b] X_on[i][a, b] + sum_{e: erow[e] = i}
     sum_b P_off[e][a, b] X_off[e][a, b], per_atom its sum over a.  With overlap rows: the Mulliken populations (their total is sum_s f_s for S-normalised
     states); with Hamiltonian rows the atoms' shares of sum_s f_s eps_s.  Fixed-order sums: two calls are bit-identical."""
-    nao = int(tables["nao"])
+    nao = tables.nao
     N, E = int(P_on.shape[0]), int(P_off.shape[0])
     if tuple(P_on.shape) != (N, nao * nao) or tuple(X_on.shape) != (N, nao * nao) or tuple(P_off.shape) != (E, nao * nao) or tuple(X_off.shape) != (E, nao * nao) \
-            or tuple(tables["erow"].shape) != (E,):
-        raise ValueError(f"populations: P_on / X_on must be [N, {nao * nao}], P_off / X_off [E, {nao * nao}] with the tables' {int(tables['erow'].shape[0])} edges, got "
+            or tuple(tables.erow.shape) != (E,):
+        raise ValueError(f"populations: P_on / X_on must be [N, {nao * nao}], P_off / X_off [E, {nao * nao}] with the tables' {int(tables.erow.shape[0])} edges, got "
                          f"{tuple(P_on.shape)}, {tuple(X_on.shape)}, {tuple(P_off.shape)}, {tuple(X_off.shape)}")
     on = (P_on * X_on).reshape(N, nao, nao).sum(2)
     off = (P_off * X_off).reshape(E, nao, nao).sum(2)
-    per_orbital = on + _fixed_order_sum(tables["erow"], off, N)
+    per_orbital = on + _fixed_order_sum(tables.erow, off, N)
     return per_orbital.sum(1), per_orbital
 
 

@@ -12,7 +12,10 @@ from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional
+from dataclasses import dataclass
+from functools import cached_property
+from types import SimpleNamespace
+from typing import Optional
 
 import numpy as np
 import torch
@@ -125,67 +128,99 @@ def _crystal_slices(data):
     return out
 
 
-def _pair_tables(data, n0, n, e0, e, orank_all):
-    """the tables hg_hk_assemble and its adjoint share for one crystal (rows n0:n0+n, edges e0:e0+e; integer plumbing): edges grouped by
-    atom pair -> (pair_ptr [npairs + 1], pair_edges [e] crystal-local edge ids, pair_ij [npairs, 2], orank [n, nao], ooff [n] int32, M)"""
-    dev = orank_all.device
-    src = (data.edge_index[0][e0:e0 + e] - n0).contiguous()
-    dst = (data.edge_index[1][e0:e0 + e] - n0).contiguous()
-    key = src * n + dst
-    order = torch.sort(key, stable=True).indices
-    uniq, counts = torch.unique_consecutive(key[order], return_counts=True)
-    ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
-    ptr[1:] = torch.cumsum(counts, 0)
-    pij = torch.stack([uniq // n, uniq % n], 1).contiguous()
-    orank = orank_all[n0:n0 + n].contiguous()
-    norb = (orank >= 0).sum(1)
-    ooff = (torch.cumsum(norb, 0) - norb).to(torch.int32).contiguous()
-    return ptr, order.contiguous(), pij, orank, ooff, int(norb.sum())
+@dataclass(frozen=True, eq=False)
+class CrystalTables:
+    """The integer tables of one crystal that every consumer of the compact orbital basis reads (hg_hk_assemble and its adjoint, hg_bond_weights,
+    hg_density_rows, the torch paths): built once per crystal and handed on.  n0, n, e0, e: the crystal's rows and edges inside the batch; orank int32
+    [n, nao]: rank of an orbital inside its element's valid set or -1; ooff int32 [n]: first compact index of every atom; M: number of compact
+    orbitals; erow / ecol int32 [e]: crystal-local row / column atom of every edge (edge_index[0] / [1]); shift fp32 [e, 3]: the shift the tables
+    were GIVEN -- the Cartesian nbr_shift of the graph for the assembly (from_graph, with Cartesian k-vectors), integer cell shifts for the reduced-k
+    convention of bonds.py (from_edges); only k . shift is ever formed.  The edges grouped by atom pair (pair_ptr, pair_edges, pair_ij) are only read
+    by the assembly and its adjoint: computed at first use, then kept."""
+    n0: int
+    n: int
+    e0: int
+    e: int
+    nao: int
+    M: int
+    orank: torch.Tensor
+    ooff: torch.Tensor
+    erow: torch.Tensor
+    ecol: torch.Tensor
+    shift: torch.Tensor
+
+    @classmethod
+    def from_graph(cls, data, n0, n, e0, e, orank_all):
+        """rows n0:n0+n and edges e0:e0+e of a (batched) graph; orank_all [N, nao]: the head's rank table gathered by data.z; shift = data.nbr_shift
+        rounded to fp32, what the kernels read -- so the torch adjoint of a graph with an fp64 nbr_shift now sees the forward's shifts, not the fp64 ones"""
+        orank = orank_all[n0:n0 + n].to(torch.int32).contiguous()
+        norb = (orank >= 0).sum(1)
+        ooff = (torch.cumsum(norb, 0) - norb).to(torch.int32).contiguous()
+        erow, ecol = ((data.edge_index[r][e0:e0 + e] - n0).to(torch.int32).contiguous() for r in (0, 1))
+        return cls(n0, n, e0, e, int(orank.shape[1]), int(norb.sum()), orank, ooff, erow, ecol, data.nbr_shift[e0:e0 + e].float().contiguous())
+
+    @classmethod
+    def from_edges(cls, edge_index, shift, z, orank_by_z, device):
+        """one whole crystal on `device` from host or device arrays: edge_index [2, E], shift [E, 3], z [N], orank_by_z [119, nao] (basis.orbital_rank_table)"""
+        t = lambda a, dt: torch.as_tensor(a).to(device=device, dtype=dt)
+        z = t(z, torch.int64).reshape(-1)
+        graph = SimpleNamespace(edge_index=t(edge_index, torch.int64), nbr_shift=t(shift, torch.float32).reshape(-1, 3))
+        return cls.from_graph(graph, 0, int(z.shape[0]), 0, int(graph.nbr_shift.shape[0]), t(orank_by_z, torch.int32)[z])
+
+    @cached_property
+    def _pairs(self):
+        """edges grouped by atom pair, in the order of a stable sort of row * n + column"""
+        key = self.erow.long() * self.n + self.ecol.long()
+        order = torch.sort(key, stable=True).indices
+        uniq, counts = torch.unique_consecutive(key[order], return_counts=True)
+        ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=key.device)
+        ptr[1:] = torch.cumsum(counts, 0)
+        return ptr, order.contiguous(), torch.stack([uniq // self.n, uniq % self.n], 1).contiguous()
+
+    pair_ptr = property(lambda self: self._pairs[0], doc="int64 [npairs + 1]: the edges of pair p are pair_edges[pair_ptr[p]:pair_ptr[p + 1]]")
+    pair_edges = property(lambda self: self._pairs[1], doc="int64 [e]: crystal-local edge ids, grouped by pair")
+    pair_ij = property(lambda self: self._pairs[2], doc="int64 [npairs, 2]: (row atom, column atom) of every pair that has an edge")
+
+    def __getitem__(self, name):
+        """tab["erow"]: reading a field by its name, as from the dict bonds.bond_tables used to return (reading only: the object is no mapping)"""
+        return getattr(self, name)
+
+    @cached_property
+    def compact_index(self):
+        """int64 [n, nao]: compact orbital index of (atom, orbital) inside the crystal, or -1"""
+        return torch.where(self.orank >= 0, self.ooff[:, None] + self.orank, torch.full_like(self.orank, -1)).long()
 
 
-def assemble_k(on, off, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
-    """[nk, M, M] complex64 of one crystal (rows n0:n0+n, edges e0:e0+e) from planar [.., nao^2] blocks"""
-    ptr, order, pij, orank, ooff, M = _pair_tables(data, n0, n, e0, e, orank_all)
-    return ops.hk_assemble(on[n0:n0 + n].contiguous(), off[e0:e0 + e].contiguous(), data.nbr_shift[e0:e0 + e].contiguous().float(),
-                           k_vecs_c.contiguous().float(), ptr, order, pij, n, nao, orank, ooff, M), M
+def assemble_k(on, off, tab, kvec):
+    """[nk, M, M] complex64 of one crystal (the rows and edges of `tab`) from planar [.., nao^2] blocks of the batch"""
+    return ops.hk_assemble(on[tab.n0:tab.n0 + tab.n].contiguous(), off[tab.e0:tab.e0 + tab.e].contiguous(), tab.shift, kvec.contiguous().float(),
+                           tab.pair_ptr, tab.pair_edges, tab.pair_ij, tab.n, tab.nao, tab.orank, tab.ooff, tab.M)
 
 
-def _compact_index(orank_all, n0, n):
-    """[n, nao] compact orbital index of (atom, orbital) inside one crystal, or -1"""
-    orank = orank_all[n0:n0 + n]
-    norb = (orank >= 0).sum(1)
-    ooff = torch.cumsum(norb, 0) - norb
-    return torch.where(orank >= 0, ooff[:, None] + orank, torch.full_like(orank, -1)).long()
-
-
-def assemble_k_adjoint(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
+def assemble_k_adjoint(G, tab, kvec):
     """Adjoint of assemble_k (hg_hk_assemble) for one crystal: G [nk, M, M] complex = the gradient of a real loss with respect to H(k) in
     torch's convention (d/dRe + i d/dIm) -> (g_on [n, nao^2], g_off [e, nao^2]) real.  With H(k)[(i a), (j b)] = on_i[a, b] delta_ij +
     sum_{e: i -> j} exp(2 pi i k . shift_e) off_e[a, b]:  g_off_e[a, b] = sum_k Re(conj(phase_k(e)) G_k[(i a), (j b)]).
     On the GPU: the HIP kernel hg_hk_assemble_adjoint on the pair tables of assemble_k (fixed order, no temporaries).  CPU tensors, and
     HG_HK_ADJOINT=torch on the GPU, take the torch path below."""
     if G.is_cuda and os.environ.get("HG_HK_ADJOINT", "").lower() != "torch":
-        ptr, order, pij, orank, ooff, M = _pair_tables(data, n0, n, e0, e, orank_all)
-        return ops.hk_assemble_adjoint(G.to(torch.complex64), data.nbr_shift[e0:e0 + e].contiguous().float(), k_vecs_c.contiguous().float(), ptr, order,
-                                       pij, n, e, nao, orank, ooff, M)
-    return _assemble_k_adjoint_torch(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao)
+        return ops.hk_assemble_adjoint(G.to(torch.complex64), tab.shift, kvec.contiguous().float(), tab.pair_ptr, tab.pair_edges, tab.pair_ij,
+                                       tab.n, tab.e, tab.nao, tab.orank, tab.ooff, tab.M)
+    return _assemble_k_adjoint_torch(G, tab, kvec)
 
 
-def _assemble_k_adjoint_torch(G, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
+def _assemble_k_adjoint_torch(G, tab, kvec):
     """assemble_k_adjoint as gathers and one complex multiply-reduce per chunk of k (torch tensor ops; device-agnostic, any precision,
     checked on CPU against autograd; [8, e, nao, nao] complex temporaries per chunk)"""
-    comp = _compact_index(orank_all, n0, n)                    # [n, nao]
-    src = (data.edge_index[0][e0:e0 + e] - n0).long()
-    dst = (data.edge_index[1][e0:e0 + e] - n0).long()
+    comp, n, e, nao = tab.compact_index, tab.n, tab.e, tab.nao  # [n, nao]
     nk = G.shape[0]
     rdt = G.real.dtype
     ok_on = ((comp[:, :, None] >= 0) & (comp[:, None, :] >= 0)).to(rdt)
     Gon = G[:, comp.clamp(min=0)[:, :, None], comp.clamp(min=0)[:, None, :]]                # [nk, n, nao, nao]
     g_on = (Gon.real.sum(0) * ok_on).reshape(n, nao * nao)
-    R, Cc = comp[src], comp[dst]
+    R, Cc = comp[tab.erow.long()], comp[tab.ecol.long()]
     ok = ((R[:, :, None] >= 0) & (Cc[:, None, :] >= 0)).to(rdt)
-    shift = data.nbr_shift[e0:e0 + e].to(torch.float64)
-    ph = 2.0 * math.pi * (k_vecs_c.to(torch.float64)[:, None, :] * shift[None, :, :]).sum(-1)      # [nk, e] in double (see the kernel)
+    ph = 2.0 * math.pi * (kvec.to(torch.float64)[:, None, :] * tab.shift.to(torch.float64)[None, :, :]).sum(-1)  # [nk, e] in double (see the kernel)
     cph = torch.complex(torch.cos(ph), -torch.sin(ph)).to(G.dtype)                               # conj(phase)
     g_off = torch.zeros(e, nao, nao, device=G.device, dtype=rdt)
     for k0 in range(0, nk, 8):
@@ -250,13 +285,6 @@ def _shard_of(data):
     return tuple(int(v) for v in data.get("_hg_shard"))
 
 
-def _single_crystal(data):
-    sl = _crystal_slices(data)
-    if len(sl) != 1:
-        raise ValueError("the k-space step on an edge-sharded graph: a sharded graph holds exactly one crystal")
-    return sl
-
-
 def _own_onsite(on, shard):
     """the replicated on-site rows enter the summed assembly once: on rank 0"""
     return on if shard is None or shard[0] == 0 else torch.zeros_like(on)
@@ -301,41 +329,55 @@ def broadcast_k_vectors(k_vecs, data):
     return k_vecs
 
 
+def _solve_k_block(shard, nk, solve, empty):
+    """the tensors `solve(k0, k1)` returns for this rank's block of k-points ([k1 - k0, ...] each; the tuple `empty` of [0, ...] zeros where the rank
+    has no k-point), gathered to [nk, ...] in k order on every rank.  Every rank joins the gathers."""
+    k0, k1 = _k_block(shard, nk)
+    return tuple(_gather_k(t, shard, nk) for t in (solve(k0, k1) if k1 > k0 else empty))
+
+
 def _eig_chain_sharded(head, Hk, Sk, val_c, z_c, shard):
     """_eig_chain on the summed H(k), S(k) of a sharded crystal: this rank solves its k-block, the blocks are gathered"""
     nk, M = int(Hk.shape[0]), int(Hk.shape[1])
-    k0, k1 = _k_block(shard, nk)
-    if k1 > k0:
-        evals, evecs, Ht = _eig_solve(Hk[k0:k1], Sk[k0:k1])
-    else:
-        evals, evecs, Ht = Hk.real.new_zeros(0, M), Hk.new_zeros(0, M, M), Hk.new_zeros(0, M, M)
-    evals, evecs, Ht = (_gather_k(t, shard, nk) for t in (evals, evecs, Ht))
+    evals, evecs, Ht = _solve_k_block(shard, nk, lambda k0, k1: _eig_solve(Hk[k0:k1], Sk[k0:k1]),
+                                      (Hk.real.new_zeros(0, M), Hk.new_zeros(0, M, M), Hk.new_zeros(0, M, M)))
     evals, evecs, gap = _gap_and_window(head, evals, evecs, val_c, z_c)
     return evals, evecs, Ht, gap
+
+
+def _crystals(name, head, rows, data, k_vecs):
+    """The opening every public function of the k-space step shares -> (shard, Son, Soff, crystals): `shard` = (rank, world) of an edge-sharded graph or
+    None, the reference overlap rows in fp32 (the rank's own: _own_onsite), and an iterator over the crystals of the batch (the one crystal of a sharded
+    graph) that yields (tab, kvec, val_c, z_c): the crystal's CrystalTables -- built here, once -- its k-vectors [nk, 3], and the valence electrons and
+    species of its atoms.  `rows`: any of the caller's row tensors (its device is where the tables go); `name`: the caller, for the error."""
+    dev = rows.device
+    k_vecs = gget(data, "k_vecs") if k_vecs is None else k_vecs
+    if k_vecs is None:
+        raise ValueError(f"{name}: no k-vectors (data.k_vecs)")
+    k_vecs = k_vecs.to(dev)
+    z = data.z
+    orank_all = head._orank.to(dev)[z]                         # [N, nao] rank of an orbital in its element's valid set or -1
+    val = head._num_valence.to(dev)[z].to(torch.float64)
+    shard = _shard_of(data)
+    slices = _crystal_slices(data)
+    if shard is not None and len(slices) != 1:
+        raise ValueError("the k-space step on an edge-sharded graph: a sharded graph holds exactly one crystal")
+    crystals = ((CrystalTables.from_graph(data, n0, n, e0, e, orank_all), k_vecs[c], val[n0:n0 + n], z[n0:n0 + n]) for c, (n0, n, e0, e) in enumerate(slices))
+    return shard, _own_onsite(data.Son.contiguous().float(), shard), data.Soff.contiguous().float(), crystals
 
 
 def band_energies(head, onsite_hamiltonian, offsite_hamiltonian, data, k_vecs: Optional[torch.Tensor] = None):
     """calculate_band_energies(onsite, offsite, data) of the reference (:1675-1996, export_reciprocal_values=False): returns
     (band_energy [sum_c bands_c, num_k], wavefunction (flattened), band_gap [n_crystals], H_sym (flattened))."""
-    nao = head.nao_max
-    dev = onsite_hamiltonian.device
-    k_vecs = gget(data, "k_vecs") if k_vecs is None else k_vecs
-    if k_vecs is None:
-        raise ValueError("band_energies: no k-vectors (data.k_vecs)")
-    k_vecs = k_vecs.to(dev)
-    z = data.z
-    orank_all = head._orank.to(dev)[z]                         # [N, nao] rank of an orbital in its element's valid set or -1
-    val = head._num_valence.to(dev)[z].to(torch.float64)
+    shard, Son, Soff, crystals = _crystals("band_energies", head, onsite_hamiltonian, data, k_vecs)
     energies, waves, gaps, hsyms = [], [], [], []
-    Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
-    shard = _shard_of(data)
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
-        Hk, M = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sk, _ = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+    for tab, kvec, val_c, z_c in crystals:
+        Hk = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, tab, kvec)
+        Sk = assemble_k(Son, Soff, tab, kvec)
         if shard is None:
-            evals, evecs, Ht, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+            evals, evecs, Ht, gap = _eig_chain(head, Hk, Sk, val_c, z_c)
         else:
-            evals, evecs, Ht, gap = _eig_chain_sharded(head, _sum_over_ranks(Hk), _sum_over_ranks(Sk), val[n0:n0 + n], z[n0:n0 + n], shard)
+            evals, evecs, Ht, gap = _eig_chain_sharded(head, _sum_over_ranks(Hk), _sum_over_ranks(Sk), val_c, z_c, shard)
         gaps.append(gap)
         energies.append(evals.transpose(-1, -2))
         waves.append(evecs.reshape(-1))
@@ -354,23 +396,15 @@ def band_energies_export(head, onsite_hamiltonian, offsite_hamiltonian, data, ov
         raise NotImplementedError("export_reciprocal_values on an edge-sharded graph is not built: H(k), S(k) and dS(k) would be those of the rank's "
                                   "own edges only; run the export on the whole crystal")
     nao = head.nao_max
-    dev = onsite_hamiltonian.device
-    k_vecs = gget(data, "k_vecs") if k_vecs is None else k_vecs
-    if k_vecs is None:
-        raise ValueError("band_energies_export: no k-vectors (data.k_vecs)")
-    k_vecs = k_vecs.to(dev)
-    z = data.z
-    orank_all = head._orank.to(dev)[z]
-    val = head._num_valence.to(dev)[z].to(torch.float64)
-    Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
+    _, Son, Soff, crystals = _crystals("band_energies_export", head, onsite_hamiltonian, data, k_vecs)
     dSon, dSoff = data.dSon.float().reshape(Son.shape[0], nao * nao, 3), data.dSoff.float().reshape(Soff.shape[0], nao * nao, 3)
     energies, waves, gaps, HKs, SKs, dSKs = [], [], [], [], [], []
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data)):
-        Hk, M = assemble_k(onsite_hamiltonian, offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sk, _ = assemble_k(Son, Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sp = Sk if overlap is None else assemble_k(overlap[0].contiguous().float(), overlap[1].contiguous().float(), data, k_vecs[c], n0, n, e0, e, orank_all, nao)[0]
-        dSk = torch.stack([assemble_k(dSon[..., d].contiguous(), dSoff[..., d].contiguous(), data, k_vecs[c], n0, n, e0, e, orank_all, nao)[0] for d in range(3)], -1)
-        evals, evecs, _, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+    for tab, kvec, val_c, z_c in crystals:
+        Hk = assemble_k(onsite_hamiltonian, offsite_hamiltonian, tab, kvec)
+        Sk = assemble_k(Son, Soff, tab, kvec)
+        Sp = Sk if overlap is None else assemble_k(overlap[0].contiguous().float(), overlap[1].contiguous().float(), tab, kvec)
+        dSk = torch.stack([assemble_k(dSon[..., d].contiguous(), dSoff[..., d].contiguous(), tab, kvec) for d in range(3)], -1)
+        evals, evecs, _, gap = _eig_chain(head, Hk, Sk, val_c, z_c)
         norm = torch.einsum("nai,nij,naj->na", evecs.conj(), Sk, evecs).real
         evecs = evecs * (1.0 / torch.sqrt(norm)).unsqueeze(-1)
         energies.append(evals.transpose(-1, -2))
@@ -424,34 +458,19 @@ def band_energies_soc(head, real_onsite, imag_onsite, real_offsite, imag_offsite
     factor of S(k) (:2236-2252, hipSOLVER through torch.linalg); band window :2254-2263 (dict: leading bands; int: +- that many bands
     around the number of valence electrons).  Edge-sharded crystal: the stacked H(k) and S(k) are summed over the ranks once each, every rank
     solves its block of k-points, eigenvalues and eigenvectors are gathered (see _eig_chain_sharded)."""
-    nao = head.nao_max
-    dev = real_onsite.device
-    k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs)
-    if k_vecs is None:
-        raise ValueError("band_energies_soc: no k-vectors (data.k_vecs)")
-    k_vecs = k_vecs.to(dev)
-    z = data.z
-    orank_all = head._orank.to(dev)[z]
-    val = head._num_valence.to(dev)[z].to(torch.float64)
-    Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
+    shard, Son, Soff, crystals = _crystals("band_energies_soc", head, real_onsite, data, k_vecs)
     energies, waves = [], []
-    shard = _shard_of(data)
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
-        Sk, M = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e,
-                     orank_all, nao)                           # [nk, 2 M, 2 M]
+    for tab, kvec, val_c, z_c in crystals:
+        M = tab.M
+        Sk = assemble_k(Son, Soff, tab, kvec)
+        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, tab, kvec)      # [nk, 2 M, 2 M]
         if shard is None:
             evals, evecs = _soc_solve(Hk, _soc_overlap(Sk, Hk, M))
         else:
             Hk, Sk = _sum_over_ranks(Hk), _sum_over_ranks(Sk)
-            nk = int(Hk.shape[0])
-            k0, k1 = _k_block(shard, nk)
-            if k1 > k0:
-                evals, evecs = _soc_solve(Hk[k0:k1], _soc_overlap(Sk[k0:k1], Hk[k0:k1], M))
-            else:
-                evals, evecs = Hk.real.new_zeros(0, 2 * M), Hk.new_zeros(0, 2 * M, 2 * M)
-            evals, evecs = _gather_k(evals, shard, nk), _gather_k(evecs, shard, nk)
-        lo, hi = _soc_window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
+            evals, evecs = _solve_k_block(shard, int(Hk.shape[0]), lambda k0, k1: _soc_solve(Hk[k0:k1], _soc_overlap(Sk[k0:k1], Hk[k0:k1], M)),
+                                          (Hk.real.new_zeros(0, 2 * M), Hk.new_zeros(0, 2 * M, 2 * M)))
+        lo, hi = _soc_window_bounds(head, val_c, z_c)
         if lo is not None:
             evals, evecs = evals[:, lo:hi], evecs[:, lo:hi, :]
         energies.append(evals.transpose(-1, -2))
@@ -465,23 +484,19 @@ def _sharded_chain_gradient(solve, Hk, shard, cot_window, lo, hi, gap=None):
     of the cotangent, and the blocks of G are gathered.  gap: (half, cotangent scalar) -- the gap is min_k evals[:, half] - max_k evals[:, half - 1], so
     its cotangent is one-hot at the arg-min / arg-max of the GATHERED eigenvalues and joins the band cotangent: one chain per k-point."""
     nk, nb_all = int(Hk.shape[0]), int(Hk.shape[1])
+    C = torch.zeros(nk, nb_all, device=Hk.device, dtype=Hk.real.dtype)
+    if cot_window is not None:
+        C[:, lo:hi] = cot_window.to(C.dtype).transpose(0, 1)
     k0, k1 = _k_block(shard, nk)
     with torch.enable_grad():
         Hb = Hk[k0:k1].detach().requires_grad_()
-        evals = solve(Hb, k0, k1) if k1 > k0 else Hk.real.new_zeros(0, nb_all)
-        C = torch.zeros(nk, nb_all, device=Hk.device, dtype=evals.dtype)
-        if cot_window is not None:
-            C[:, lo:hi] = cot_window.to(evals.dtype).transpose(0, 1)
+        evals = solve(Hb, k0, k1) if k1 > k0 else None         # solved once; both gathers below read it (no k-point: they take their zeros)
         if gap is not None:
             half, gc = gap
-            full = _gather_k(evals.detach(), shard, nk)
-            C[torch.argmin(full[:, half]), half] += gc.to(evals.dtype)
-            C[torch.argmax(full[:, half - 1]), half - 1] -= gc.to(evals.dtype)
-        if k1 > k0:
-            (Gb,) = torch.autograd.grad((evals * C[k0:k1]).sum(), Hb)
-        else:
-            Gb = torch.zeros_like(Hb)
-    return _gather_k(Gb.detach(), shard, nk)
+            (full,) = _solve_k_block(shard, nk, lambda *_: (evals.detach(),), (C.new_zeros(0, nb_all),))
+            C[torch.argmin(full[:, half]), half] += gc.to(C.dtype)
+            C[torch.argmax(full[:, half - 1]), half - 1] -= gc.to(C.dtype)
+        return _solve_k_block(shard, nk, lambda *_: torch.autograd.grad((evals * C[k0:k1]).sum(), Hb), (Hk.new_zeros(0, nb_all, nb_all),))[0]
 
 
 def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, cotangent, k_vecs: Optional[torch.Tensor] = None, gap_cotangent=None):
@@ -494,24 +509,17 @@ def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, co
     rank's own edges with all k -- g_on is the whole crystal's on every rank, g_off belongs to the rank's edges (_sharded_chain_gradient)."""
     if cotangent is None and gap_cotangent is None:
         raise ValueError("band_energy_backward: neither a band-energy nor a band-gap cotangent")
-    nao = head.nao_max
-    dev = onsite_hamiltonian.device
-    k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs).to(dev)
-    z = data.z
-    orank_all = head._orank.to(dev)[z]
-    val = head._num_valence.to(dev)[z].to(torch.float64)
-    Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
+    shard, Son, Soff, crystals = _crystals("band_energy_backward", head, onsite_hamiltonian, data, k_vecs)
     g_on = torch.zeros_like(onsite_hamiltonian)
     g_off = torch.zeros_like(offsite_hamiltonian)
     row = 0
-    shard = _shard_of(data)
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
-        Hk, M = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Sk, _ = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+    for c, (tab, kvec, val_c, z_c) in enumerate(crystals):
+        Hk = assemble_k(_own_onsite(onsite_hamiltonian, shard), offsite_hamiltonian, tab, kvec)
+        Sk = assemble_k(Son, Soff, tab, kvec)
         if shard is None:
             with torch.enable_grad():
                 Hk = Hk.detach().requires_grad_()
-                evals, _, _, gap = _eig_chain(head, Hk, Sk, val[n0:n0 + n], z[n0:n0 + n])
+                evals, _, _, gap = _eig_chain(head, Hk, Sk, val_c, z_c)
                 evals = evals.transpose(-1, -2)                    # [bands, nk]
                 nb = evals.shape[0]
                 scalar = 0.0
@@ -522,27 +530,26 @@ def band_energy_backward(head, onsite_hamiltonian, offsite_hamiltonian, data, co
                 (G,) = torch.autograd.grad(scalar, Hk)
         else:
             Hk, Sk = _sum_over_ranks(Hk), _sum_over_ranks(Sk)
-            half, lo, hi = _window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
-            nb = len(range(M)[slice(lo, hi)])
+            half, lo, hi = _window_bounds(head, val_c, z_c)
+            nb = len(range(tab.M)[slice(lo, hi)])
             G = _sharded_chain_gradient(lambda Hb, k0, k1: _eig_solve(Hb, Sk[k0:k1])[0], Hk, shard,
                                         None if cotangent is None else cotangent[row:row + nb], lo, hi,
                                         gap=None if gap_cotangent is None else (half, gap_cotangent[c]))
         row += nb
-        a, b = assemble_k_adjoint(G, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        g_on[n0:n0 + n] = a
-        g_off[e0:e0 + e] = b
+        g_on[tab.n0:tab.n0 + tab.n], g_off[tab.e0:tab.e0 + tab.e] = assemble_k_adjoint(G, tab, kvec)
     return g_on, g_off
 
 
-def _soc_hk(real_onsite, imag_onsite, real_offsite, imag_offsite, data, k_vecs_c, n0, n, e0, e, orank_all, nao):
+def _soc_hk(real_onsite, imag_onsite, real_offsite, imag_offsite, tab, kvec):
     """spinor H(k) [nk, 2 M, 2 M] of one crystal: four spin blocks, each the assembly of its real part + i x the assembly of its imaginary part"""
+    nao = tab.nao
     blk = lambda t, a, b: t.reshape(-1, 2, nao, 2, nao)[:, a, :, b, :].reshape(-1, nao * nao).contiguous().float()
     rows = []
     for a in (0, 1):
         cols = []
         for b in (0, 1):
-            Hr, _ = assemble_k(blk(real_onsite, a, b), blk(real_offsite, a, b), data, k_vecs_c, n0, n, e0, e, orank_all, nao)
-            Hi, _ = assemble_k(blk(imag_onsite, a, b), blk(imag_offsite, a, b), data, k_vecs_c, n0, n, e0, e, orank_all, nao)
+            Hr = assemble_k(blk(real_onsite, a, b), blk(real_offsite, a, b), tab, kvec)
+            Hi = assemble_k(blk(imag_onsite, a, b), blk(imag_offsite, a, b), tab, kvec)
             cols.append(Hr + 1j * Hi)
         rows.append(torch.cat(cols, -1))
     return torch.cat(rows, -2)
@@ -556,20 +563,14 @@ def band_energy_backward_soc(head, real_onsite, imag_onsite, real_offsite, imag_
     with the real-linear assembly A).  Returns (g_real_on, g_imag_on, g_real_off, g_imag_off) in the rows' [., 2, nao, 2, nao] layout.
     Edge-sharded crystal: as band_energy_backward (the on-site gradients are the whole crystal's on every rank)."""
     nao = head.nao_max
-    dev = real_onsite.device
-    k_vecs = (gget(data, "k_vecs") if k_vecs is None else k_vecs).to(dev)
-    z = data.z
-    orank_all = head._orank.to(dev)[z]
-    val = head._num_valence.to(dev)[z].to(torch.float64)
-    Son, Soff = data.Son.contiguous().float(), data.Soff.contiguous().float()
-    g = [torch.zeros(t.shape[0], 2, nao, 2, nao, device=dev, dtype=torch.float32) for t in (real_onsite, imag_onsite, real_offsite, imag_offsite)]
+    shard, Son, Soff, crystals = _crystals("band_energy_backward_soc", head, real_onsite, data, k_vecs)
+    g = [torch.zeros(t.shape[0], 2, nao, 2, nao, device=real_onsite.device, dtype=torch.float32) for t in (real_onsite, imag_onsite, real_offsite, imag_offsite)]
     row = 0
-    shard = _shard_of(data)
-    for c, (n0, n, e0, e) in enumerate(_crystal_slices(data) if shard is None else _single_crystal(data)):
-        Sk, M = assemble_k(_own_onsite(Son, shard), Soff, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, data, k_vecs[c], n0, n, e0, e,
-                     orank_all, nao)
-        lo, hi = _soc_window_bounds(head, val[n0:n0 + n], z[n0:n0 + n])
+    for tab, kvec, val_c, z_c in crystals:
+        M, (n0, n, e0, e) = tab.M, (tab.n0, tab.n, tab.e0, tab.e)
+        Sk = assemble_k(Son, Soff, tab, kvec)
+        Hk = _soc_hk(_own_onsite(real_onsite, shard), _own_onsite(imag_onsite, shard), real_offsite, imag_offsite, tab, kvec)
+        lo, hi = _soc_window_bounds(head, val_c, z_c)
         if shard is None:
             Ssoc = _soc_overlap(Sk, Hk, M)
             with torch.enable_grad():
@@ -589,8 +590,8 @@ def band_energy_backward_soc(head, real_onsite, imag_onsite, real_offsite, imag_
         for a in (0, 1):
             for b in (0, 1):
                 Gab = G[:, a * M:(a + 1) * M, b * M:(b + 1) * M]
-                r_on, r_off = assemble_k_adjoint(Gab, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
-                i_on, i_off = assemble_k_adjoint(-1j * Gab, data, k_vecs[c], n0, n, e0, e, orank_all, nao)
+                r_on, r_off = assemble_k_adjoint(Gab, tab, kvec)
+                i_on, i_off = assemble_k_adjoint(-1j * Gab, tab, kvec)
                 g[0][n0:n0 + n, a, :, b, :] = r_on.reshape(n, nao, nao)
                 g[1][n0:n0 + n, a, :, b, :] = i_on.reshape(n, nao, nao)
                 g[2][e0:e0 + e, a, :, b, :] = r_off.reshape(e, nao, nao)

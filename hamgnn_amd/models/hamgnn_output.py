@@ -111,9 +111,7 @@ class HamGNNPlusPlusOut(hnn.CompiledModule, nn.Module):
         for Z, orb in self.basis_def.items():
             mask[Z, orb] = 1.0
         self._mask = torch.from_numpy(mask).to(dev)
-        orank = np.full((119, self.nao_max), -1, dtype=np.int32)           # k-space step: rank of an orbital inside its element's valid set
-        for Z, orb in self.basis_def.items():
-            orank[Z, sorted(orb)] = np.arange(len(orb), dtype=np.int32)
+        orank = B.orbital_rank_table(self.basis_def, self.nao_max)         # k-space step: rank of an orbital inside its element's valid set
         nval = np.zeros(119, dtype=np.float32)
         for Z, cnt in self.num_valence.items():
             nval[int(Z)] = cnt

@@ -936,79 +936,73 @@ def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, ep
     aidx[aptr[g]:aptr[g + 1]]), pad columns 0 (see include/hamgnn_hip.h:hg_bond_weights); every element is written.  kidx int32 [ns] -> rows of kvec
     [nk, 3]; erow / ecol int32 [E], shift [E, 3]; orank int32 [N, nao], ooff int32 [N].  All tables are checked here, on the host, before the launch."""
     _require_gpu(C_)               # (the tables are read below, ahead of the launch)
-    if C_.dim() != 2 or C_.dtype != torch.complex64:
-        raise ValueError(f"bond_weights: C must be complex64 [ns, M], got {C_.dtype} {tuple(C_.shape)}")
-    ns, M = int(C_.shape[0]), int(C_.shape[1])
-    if orank.dim() != 2:
-        raise ValueError(f"bond_weights: orank must be [N, nao], got {tuple(orank.shape)}")
-    N, nao = int(orank.shape[0]), int(orank.shape[1])
-    E, nk, G = int(X_off.shape[0]), int(kvec.shape[0]), int(eptr.shape[0]) - 1
-    shapes = {"kvec": (kvec, (nk, 3)), "X_on": (X_on, (N, nao * nao)), "X_off": (X_off, (E, nao * nao)), "shift": (shift, (E, 3)), "wk": (wk, (ns,)), "kidx": (kidx, (ns,)),
-              "erow": (erow, (E,)), "ecol": (ecol, (E,)), "ooff": (ooff, (N,)), "eptr": (eptr, (G + 1,)), "aptr": (aptr, (G + 1,)), "eidx": (eidx, (int(eidx.numel()),)),
-              "aidx": (aidx, (int(aidx.numel()),))}
-    for name, (t, shape) in shapes.items():
-        if tuple(t.shape) != shape:
-            raise ValueError(f"bond_weights: {name} must be {list(shape)}, got {list(t.shape)}")
-        if t.device != C_.device:                              # (the typed call asks for a GPU tensor, not for this GPU)
-            raise ValueError(f"bond_weights: {name} is on {t.device}, C on {C_.device}")
+    G = int(eptr.shape[0]) - 1 if eptr.dim() else -1
+    i32, f32 = torch.int32, torch.float32
+    ns, M, N, nao, E, nk = check_state_tables("bond_weights", C_, kidx, kvec, erow, ecol, shift, orank, ooff, extra=(
+        ("X_on", X_on, ("N", "nao2"), f32), ("X_off", X_off, ("E", "nao2"), f32), ("wk", wk, ("ns",), f32), ("eptr", eptr, (G + 1,), i32),
+        ("aptr", aptr, (G + 1,), i32), ("eidx", eidx, (int(eidx.numel()),), i32), ("aidx", aidx, (int(aidx.numel()),), i32)))
     if G < 0 or Gp < 1 + G:
         raise ValueError(f"bond_weights: Gp = {Gp} holds no room for the state weight and {G} groups")
-    if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
-        raise ValueError(f"bond_weights: needs at least one atom, one k-point and one orbital and nao <= 48, got N = {N}, nk = {nk}, M = {M}, nao = {nao}")
-
-    def in_range(name, t, n):                                  # (host checks of the index tables: a device-to-host copy of two scalars each)
-        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
-            raise ValueError(f"bond_weights: {name} has entries outside [0, {n})")
-    in_range("kidx", kidx, nk), in_range("erow", erow, N), in_range("ecol", ecol, N), in_range("eidx", eidx, E), in_range("aidx", aidx, N)
-    for name, p, idx in (("eptr", eptr, eidx), ("aptr", aptr, aidx)):
+    for name, p, iname, idx, n in (("eptr", eptr, "eidx", eidx, E), ("aptr", aptr, "aidx", aidx, N)):
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise ValueError(f"bond_weights: {iname} has entries outside [0, {n})")
         ph = p.cpu()
         if int(ph[0]) != 0 or int(ph[-1]) != idx.numel() or bool((ph[1:] < ph[:-1]).any()):
             raise ValueError(f"bond_weights: {name} must ascend from 0 to the {idx.numel()} entries of its index list")
-    top = torch.where(orank >= 0, ooff[:, None] + orank, torch.zeros_like(orank))
-    if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
-        raise ValueError(f"bond_weights: orank / ooff point outside the {M} compact orbitals of C")
     W = torch.empty(ns, Gp, device=C_.device, dtype=torch.float32)
     call("hg_bond_weights", torch.view_as_real(C_), ns, M, kidx, kvec, nk, X_on, X_off, erow, ecol, shift, E, N, nao, orank, ooff, eptr, eidx, aptr, aidx, G, Gp, wk, W)
     return W
 
 
-def density_rows_check(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out, accumulate):
-    """the host checks of density_rows (any device; the torch path of hamgnn_amd/density.py runs them too): dtypes, shapes, devices, the index ranges of kidx /
-    erow / ecol, orank / ooff inside the M columns of C, `out` = (P_on, P_off) where accumulate adds to it; each ValueError names its argument -> (ns, M, N, nao, E, nk)"""
+def check_state_tables(who, C_, kidx, kvec, erow, ecol, shift, orank, ooff, extra=()):
+    """The host checks the kernels on eigenvector rows share (hg_bond_weights, hg_density_rows; any device, so the torch paths run them too): C_ complex64
+    [ns, M]; kidx int32 [ns] -> rows of kvec fp32 [nk, 3]; erow / ecol int32 [E] -> atoms, shift fp32 [E, 3]; orank int32 [N, nao], ooff int32 [N] inside the
+    M columns of C_.  extra: (name, tensor, shape, dtype) of the caller's further tensors, a shape entry either a number or one of "ns", "M", "N", "nao",
+    "nao2", "E", "nk".  dtype, shape, device and contiguity of every tensor, then the index ranges (a device-to-host copy of two scalars each).  Each
+    ValueError starts with `who` and names its argument -> (ns, M, N, nao, E, nk)"""
     if not isinstance(C_, torch.Tensor) or C_.dim() != 2 or C_.dtype != torch.complex64:
-        raise ValueError(f"density_rows: C must be complex64 [ns, M], got {getattr(C_, 'dtype', type(C_).__name__)} {tuple(getattr(C_, 'shape', ()))}")
+        raise ValueError(f"{who}: C must be complex64 [ns, M], got {getattr(C_, 'dtype', type(C_).__name__)} {tuple(getattr(C_, 'shape', ()))}")
     ns, M = int(C_.shape[0]), int(C_.shape[1])
     if orank.dim() != 2:
-        raise ValueError(f"density_rows: orank must be [N, nao], got {tuple(orank.shape)}")
+        raise ValueError(f"{who}: orank must be [N, nao], got {tuple(orank.shape)}")
     N, nao = int(orank.shape[0]), int(orank.shape[1])
     E, nk = int(erow.shape[0]) if erow.dim() else -1, int(kvec.shape[0]) if kvec.dim() else -1
+    dims = {"ns": ns, "M": M, "N": N, "nao": nao, "nao2": nao * nao, "E": E, "nk": nk}
     i32, f32 = torch.int32, torch.float32
-    named = {"kidx": (kidx, (ns,), i32), "kvec": (kvec, (nk, 3), f32), "f": (f, (ns,), f32), "erow": (erow, (E,), i32), "ecol": (ecol, (E,), i32),
-             "shift": (shift, (E, 3), f32), "orank": (orank, (N, nao), i32), "ooff": (ooff, (N,), i32)}
+    named = (("kidx", kidx, ("ns",), i32), ("kvec", kvec, ("nk", 3), f32), ("erow", erow, ("E",), i32), ("ecol", ecol, ("E",), i32),
+             ("shift", shift, ("E", 3), f32), ("orank", orank, ("N", "nao"), i32), ("ooff", ooff, ("N",), i32)) + tuple(extra)
+    for name, t, shape, dtype in named:
+        shape = tuple(dims.get(d, d) for d in shape)
+        if t.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be {dtype}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{who}: {name} must be {list(shape)}, got {list(t.shape)}")
+        if t.device != C_.device:                              # (the typed call asks for a GPU tensor, not for this GPU)
+            raise ValueError(f"{who}: {name} is on {t.device}, C on {C_.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
+        raise ValueError(f"{who}: needs at least one atom, one k-point and one orbital and nao <= 48, got N = {N}, nk = {nk}, M = {M}, nao = {nao}")
+    for name, t, n in (("kidx", kidx, nk), ("erow", erow, N), ("ecol", ecol, N)):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError(f"{who}: {name} has entries outside [0, {n})")
+    top = torch.where(orank >= 0, ooff[:, None] + orank, torch.zeros_like(orank))
+    if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
+        raise ValueError(f"{who}: orank / ooff point outside the {M} compact orbitals of C")
+    return ns, M, N, nao, E, nk
+
+
+def density_rows_check(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out, accumulate):
+    """the host checks of density_rows (any device; the torch path of hamgnn_amd/density.py runs them too): check_state_tables with f and, where given,
+    `out` = (P_on, P_off), which accumulate needs -> (ns, M, N, nao, E, nk)"""
+    extra = [("f", f, ("ns",), torch.float32)]
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 2:
             raise ValueError("density_rows: out must be the pair (P_on, P_off)")
-        named["out[0] (P_on)"], named["out[1] (P_off)"] = (out[0], (N, nao * nao), f32), (out[1], (E, nao * nao), f32)
+        extra += [("out[0] (P_on)", out[0], ("N", "nao2"), torch.float32), ("out[1] (P_off)", out[1], ("E", "nao2"), torch.float32)]
     elif accumulate:
         raise ValueError("density_rows: accumulate needs the out = (P_on, P_off) to add to")
-    for name, (t, shape, dtype) in named.items():
-        if t.dtype != dtype:
-            raise ValueError(f"density_rows: {name} must be {dtype}, got {t.dtype}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"density_rows: {name} must be {list(shape)}, got {list(t.shape)}")
-        if t.device != C_.device:
-            raise ValueError(f"density_rows: {name} is on {t.device}, C on {C_.device}")
-        if not t.is_contiguous():
-            raise ValueError(f"density_rows: {name} must be contiguous")
-    if N < 1 or nk < 1 or M < 1 or not 1 <= nao <= 48:
-        raise ValueError(f"density_rows: needs at least one atom, one k-point and one orbital and nao <= 48, got N = {N}, nk = {nk}, M = {M}, nao = {nao}")
-    for name, t, n in (("kidx", kidx, nk), ("erow", erow, N), ("ecol", ecol, N)):      # (a device-to-host copy of two scalars each)
-        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
-            raise ValueError(f"density_rows: {name} has entries outside [0, {n})")
-    top = torch.where(orank >= 0, ooff[:, None] + orank, torch.zeros_like(orank))
-    if int(orank.min()) < -1 or int(ooff.min()) < 0 or int(top.max()) >= M:
-        raise ValueError(f"density_rows: orank / ooff point outside the {M} compact orbitals of C")
-    return ns, M, N, nao, E, nk
+    return check_state_tables("density_rows", C_, kidx, kvec, erow, ecol, shift, orank, ooff, extra)
 
 
 @_on_tensor_device

@@ -43,8 +43,8 @@ def bench(nk, reps):
     g = si_diamond(2, 2, 2)
     z, ei, sh = g.z.numpy(), g.edge_index.numpy(), g.cell_shift.numpy()
     N, E = len(z), ei.shape[1]
-    tables = bonds.bond_tables(head, z, ei, sh, "cuda")
-    M = tables["M"]
+    tab = bonds.bond_tables(head, z, ei, sh, "cuda")
+    M = tab.M
     ns = nk * M
     gen = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=gen)
@@ -53,7 +53,7 @@ def bench(nk, reps):
     kvec = torch.rand(nk, 3, device="cuda", generator=gen) - 0.5
     kidx = torch.arange(nk, device="cuda", dtype=torch.int32).repeat_interleave(M)
     wk = torch.full((ns,), 1.0 / nk, device="cuda")
-    norb = (tables["orank"] >= 0).sum(1).cpu().numpy()
+    norb = (tab.orank >= 0).sum(1).cpu().numpy()
     flop = 8.0 * float((norb[ei[0]] * norb[ei[1]]).sum() + (norb * norb).sum()) * ns
     moved = C.numel() * 8 + (Xon.numel() + Xoff.numel()) * 4
     # for scale: the Mulliken projection on atoms of the same states, S(k) C by one bmm + the weight kernel
@@ -71,7 +71,7 @@ def bench(nk, reps):
         groups = tuple(torch.from_numpy(a).cuda() for a in bonds.bond_groups(ei, sh, z, by=by, onsite=True)[:4])
         G = int(groups[0].shape[0]) - 1
         Gp = dos.padded_groups(G)
-        args = (C, kidx, kvec, Xon, Xoff, tables["erow"], tables["ecol"], tables["shift"], tables["orank"], tables["ooff"], *groups, wk, Gp)
+        args = (C, kidx, kvec, Xon, Xoff, tab.erow, tab.ecol, tab.shift, tab.orank, tab.ooff, *groups, wk, Gp)
         k_ms = timed(lambda: ops.bond_weights(*args), 2, reps)
         t_ms = timed(lambda: bonds._bond_weights_torch(*args), 1, max(2, reps // 2))
         Wk, Wt = ops.bond_weights(*args), bonds._bond_weights_torch(*args)

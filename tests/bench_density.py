@@ -44,8 +44,8 @@ def bench(atoms, nk, nb, reps):
     g = random_cell(atoms, (1, 14, 34), seed=0)
     z, ei, sh = g.z.numpy(), g.edge_index.numpy(), g.cell_shift.numpy()
     N, E = len(z), ei.shape[1]
-    tables = bonds.bond_tables(head, z, ei, sh, "cuda")
-    M = tables["M"]
+    tab = bonds.bond_tables(head, z, ei, sh, "cuda")
+    M = tab.M
     ns = nk * nb
     gen = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=gen)
@@ -53,16 +53,15 @@ def bench(atoms, nk, nb, reps):
     f = rnd(ns) / nk
     kvec = torch.rand(nk, 3, device="cuda", generator=gen) - 0.5
     kidx = torch.arange(nk, device="cuda", dtype=torch.int32).repeat_interleave(nb)
-    args = (C, kidx, kvec, f, tables["erow"], tables["ecol"], tables["shift"], tables["orank"], tables["ooff"])
-    norb = (tables["orank"] >= 0).sum(1).cpu().numpy()
+    args = (C, kidx, kvec, f, tab.erow, tab.ecol, tab.shift, tab.orank, tab.ooff)
+    norb = (tab.orank >= 0).sum(1).cpu().numpy()
     pairs = float((norb[ei[0]] * norb[ei[1]]).sum() + (norb * norb).sum())
     flop = 8.0 * pairs * ns
     k_ms = timed(lambda: ops.density_rows(*args), 2, reps)
     t_ms = timed(lambda: density._density_rows_torch(*args), 1, max(2, reps // 2))
     Pk, Pt = ops.density_rows(*args), density._density_rows_torch(*args)
     Cr = torch.view_as_real(C)                                  # the launch alone, without the wrapper's host checks of the tables (a dozen scalar read-backs)
-    l_ms = timed(lambda: _lib.call("hg_density_rows", Cr, ns, M, kidx, kvec, nk, f, tables["erow"], tables["ecol"], tables["shift"], E, N, nao, tables["orank"],
-                                   tables["ooff"], 0, Pk[0], Pk[1]), 2, reps)
+    l_ms = timed(lambda: _lib.call("hg_density_rows", Cr, ns, M, kidx, kvec, nk, f, tab.erow, tab.ecol, tab.shift, E, N, nao, tab.orank, tab.ooff, 0, Pk[0], Pk[1]), 2, reps)
     diff = max(float((Pk[0] - Pt[0]).abs().max()), float((Pk[1] - Pt[1]).abs().max()))
     return {"atoms": N, "edges": E, "M": M, "nao": nao, "nk": nk, "ns": ns, "kernel_ms": k_ms, "launch_only_ms": l_ms, "torch_ms": t_ms, "torch_over_kernel": t_ms[0] / k_ms[0], "flop": flop,
             "fraction_of_f32_mfma_peak": flop / (l_ms[0] * 1e-3) / PEAK_F32_MFMA, "bytes_C_per_member_pass": 8.0 * float((norb[ei[0]] + norb[ei[1]]).sum() + norb.sum()) * ns,

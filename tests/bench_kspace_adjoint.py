@@ -23,11 +23,11 @@ gen = torch.Generator().manual_seed(0)
 g["k_vecs"] = 0.05 * torch.randn(1, a.nk, 3, generator=gen)
 g = g.to(dev)
 Hon, Hoff = g["Hon"].contiguous(), g["Hoff"].contiguous()
-orank_all = head._orank.to(dev)[g.z]
-M = int((orank_all >= 0).sum())
+n, e = g.num_nodes, g.num_edges
+tab = kspace.CrystalTables.from_graph(g, 0, n, 0, e, head._orank.to(dev)[g.z])      # (the adjoint alone reuses it, as the backward does inside one call)
+M = tab.M
 cot = torch.randn(M, a.nk, generator=gen).to(dev)
 Gk = torch.complex(torch.randn(a.nk, M, M, generator=gen), torch.randn(a.nk, M, M, generator=gen)).to(dev)
-n, e = g.num_nodes, g.num_edges
 
 
 def timed(fn):
@@ -53,7 +53,7 @@ for path in ("kernel", "torch"):
     if path == "torch":
         os.environ["HG_HK_ADJOINT"] = "torch"
     ms, mib, outs[path] = timed(lambda: kspace.band_energy_backward(head, Hon, Hoff, g, cot))
-    ms_a, mib_a, _ = timed(lambda: kspace.assemble_k_adjoint(Gk, g, g["k_vecs"][0], 0, n, 0, e, orank_all, nao))
+    ms_a, mib_a, _ = timed(lambda: kspace.assemble_k_adjoint(Gk, tab, g["k_vecs"][0]))
     res.update({f"{path}_backward_ms": ms, f"{path}_backward_peak_MiB": mib, f"{path}_adjoint_ms": ms_a, f"{path}_adjoint_peak_MiB": mib_a})
 os.environ.pop("HG_HK_ADJOINT", None)
 res["paths_max_rel_diff"] = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(outs["kernel"], outs["torch"]))

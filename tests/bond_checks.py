@@ -259,7 +259,7 @@ def run(c, groups, Gp, device, ns=None, Xon=None, Xoff=None, C=None, rows=None):
     rows = slice(0, c.ns if ns is None else ns) if rows is None else rows
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     tables = bonds.bond_tables(c.head, c.z, c.ei, c.shift, device)
-    assert tables["M"] == c.M
+    assert tables.M == c.M
     W = bonds.bond_weights(dev((c.C if C is None else C)[rows]), dev(c.kidx[rows]), dev(c.kvec), dev(c.Xon if Xon is None else Xon),
                            dev(c.Xoff if Xoff is None else Xoff), tables, groups, dev(c.wk[rows]), Gp)
     return W.cpu().numpy()

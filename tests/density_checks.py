@@ -180,7 +180,7 @@ def dev(a, device):
 def tables_of(c, device):
     from hamgnn_amd import bonds
     t = bonds.bond_tables(c.head, c.z, c.ei, c.shift, device)
-    assert t["M"] == c.M
+    assert t.M == c.M
     return t
 
 

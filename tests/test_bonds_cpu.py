@@ -79,14 +79,14 @@ def test_bond_groups_refuses_what_it_cannot_read():
 
 @pytest.mark.parametrize("nao", NAOS)
 def test_bond_tables_follow_the_assembly_convention(nao):
-    """orank / ooff / M as kspace._pair_tables and _compact_index derive them from the head's table; row / column atom = edge_index[0] / [1]"""
+    """orank / ooff / M as kspace.CrystalTables derives them from the head's table; row / column atom = edge_index[0] / [1]"""
     c = BC.case(nao)
     t = bonds.bond_tables(c.head, c.z, c.ei, c.shift, "cpu")
-    assert t["M"] == c.M and t["nao"] == nao and (t["orank"] < 0).any()
-    assert np.array_equal(t["ooff"].numpy(), c.off0[:-1]) and t["ooff"].dtype == t["orank"].dtype == t["erow"].dtype == torch.int32
+    assert t.M == c.M and t.nao == nao and (t.orank < 0).any()
+    assert np.array_equal(t.ooff.numpy(), c.off0[:-1]) and t.ooff.dtype == t.orank.dtype == t.erow.dtype == torch.int32
     for i, orb in enumerate(c.orbs):
-        assert np.array_equal(np.nonzero(t["orank"][i].numpy() >= 0)[0], orb) and np.array_equal(t["orank"][i].numpy()[orb], np.arange(len(orb)))
-    assert np.array_equal(t["erow"].numpy(), c.ei[0]) and np.array_equal(t["ecol"].numpy(), c.ei[1]) and np.array_equal(t["shift"].numpy(), c.shift)
+        assert np.array_equal(np.nonzero(t.orank[i].numpy() >= 0)[0], orb) and np.array_equal(t.orank[i].numpy()[orb], np.arange(len(orb)))
+    assert np.array_equal(t.erow.numpy(), c.ei[0]) and np.array_equal(t.ecol.numpy(), c.ei[1]) and np.array_equal(t.shift.numpy(), c.shift)
     with pytest.raises(ValueError, match="no element"):
         bonds.bond_tables(c.head, np.array([118]), np.zeros((2, 0), dtype=np.int64), np.zeros((0, 3)), "cpu")
 

@@ -1,7 +1,6 @@
 """hg_bond_weights (csrc/spectra.hip) on the GPU through hamgnn_amd/bonds.py: against the fp64 statement inside the derived bound of tests/bond_checks.py,
 its structure (every element written, bit-reproducible, rows independent of the launch), against the Mulliken kernel, the argument checks, and the chain
 into dos.tetra_states on the eigenpairs of a small crystal solved on the host."""
-import types
 
 import numpy as np
 import pytest
@@ -61,8 +60,7 @@ def test_row_atom_groups_agree_with_the_mulliken_kernel(nao):
     ref, T, kp, kk = BC.ref_bond_weights(c, groups, Gp)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     tables = bonds.bond_tables(c.head, c.z, c.ei, c.shift, "cuda")
-    data = types.SimpleNamespace(edge_index=dev(c.ei), nbr_shift=dev(c.shift.astype(np.float32)))
-    Sk, M = kspace.assemble_k(dev(c.Xon), dev(c.Xoff), data, dev(c.kvec), 0, c.N, 0, c.E, tables["orank"], nao)
+    Sk, M = kspace.assemble_k(dev(c.Xon), dev(c.Xoff), tables, dev(c.kvec)), tables.M
     assert M == c.M
     Cd = dev(c.C[:ns])
     Ck = Cd.reshape(ns // 2, 2, M).transpose(0, 1)              # [k, state, M]: the states interleave the two k-points
@@ -111,8 +109,7 @@ def test_chain_into_tetra_states_on_host_solved_eigenpairs(rows):
     c = BC.solvable_case()
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     tables = bonds.bond_tables(c.head, c.z, c.ei, c.shift, "cuda")
-    data = types.SimpleNamespace(edge_index=dev(c.ei), nbr_shift=dev(c.shift.astype(np.float32)))
-    asm = lambda on, off: kspace.assemble_k(dev(on), dev(off), data, dev(c.kvec), 0, c.N, 0, c.E, tables["orank"], c.nao)[0].cpu().numpy()
+    asm = lambda on, off: kspace.assemble_k(dev(on), dev(off), tables, dev(c.kvec)).cpu().numpy()
     eps, C = BC.solve_host(asm(c.Hon, c.Hoff), asm(c.Son, c.Soff))
     nk, nb = eps.shape
     assert (nk, nb) == (8, c.M) and np.abs(np.einsum("kbm,kbm->kb", C.conj(), C @ BC.dense_xk(c, c.Son, c.Soff, c.kvec[0]).T)[0] - 1.0).max() < 1e-5

@@ -1,6 +1,8 @@
 """hg_density_rows (csrc/spectra.hip) on the GPU through hamgnn_amd/density.py: against the fp64 statement inside the derived bound of tests/density_checks.py,
 its structure (every element written, accumulate, bit-reproducible, members independent of the launch), against the bond-weight kernel, the sum rules on
 the eigenpairs of a small crystal solved on the host, and the argument checks."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
@@ -45,7 +47,7 @@ def test_accumulate_adds_state_chunks(nao):
     the two launches' bounds (the split changes the summation order: the difference to the one launch need not be 0); elements at missing orbitals are
     written by the first launch (0) and left alone by the second"""
     c = BC.case(nao)
-    have = DC.tables_of(c, "cpu")["orank"].numpy() >= 0
+    have = DC.tables_of(c, "cpu").orank.numpy() >= 0
     miss_on = ~(have[:, :, None] & have[:, None, :]).reshape(c.N, -1)
     miss_off = ~(have[c.ei[0]][:, :, None] & have[c.ei[1]][:, None, :]).reshape(c.E, -1)
     out = (torch.full((c.N, nao * nao), 7.0, device="cuda"), torch.full((c.E, nao * nao), 7.0, device="cuda"))
@@ -166,8 +168,8 @@ def test_arguments_are_checked_on_the_host():
     for name, change in (("C", dict(C=d(c.C.astype(np.complex128)))), ("C", dict(C=wide[:, :c.M])), ("orbital columns", dict(C=d(c.C[:, :-1]))),
                          ("kidx", dict(kidx=d(bad_idx))), ("kidx", dict(kidx=d(-1 - c.kidx))), ("kidx", dict(kidx=d(c.kidx.astype(np.int64)))),
                          ("f", dict(f=d(DC.weights(c).astype(np.float64)))), ("f", dict(f=d(DC.weights(c)[:-1]))), ("f", dict(f=DC.dev(DC.weights(c), "cpu"))),
-                         ("kvec", dict(kvec=d(c.kvec[:, :2]))), ("erow", dict(tables={**t, "erow": t["erow"] + c.N})),
-                         ("ecol", dict(tables={**t, "ecol": t["ecol"].long()})), ("orank", dict(tables={**t, "ooff": t["ooff"] + 1})),
+                         ("kvec", dict(kvec=d(c.kvec[:, :2]))), ("erow", dict(tables=dataclasses.replace(t, erow=t.erow + c.N))),
+                         ("ecol", dict(tables=dataclasses.replace(t, ecol=t.ecol.long()))), ("orank", dict(tables=dataclasses.replace(t, ooff=t.ooff + 1))),
                          ("accumulate", dict(accumulate=True)), ("P_off", dict(out=(on, off[:-1]))), ("P_on", dict(out=(on.double(), off)))):
         with pytest.raises(ValueError, match=name):
             density.density_rows(**{**good, **change})

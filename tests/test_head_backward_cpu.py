@@ -96,6 +96,6 @@ def test_k_space_assembly_adjoint_vs_autograd():
     Hc = torch.masked_select(Hk, (m[:, None] & m[None, :])[None].expand(nk, -1, -1)).reshape(nk, M, M)
     G = torch.complex(torch.randn(nk, M, M, generator=gen, dtype=torch.float64), torch.randn(nk, M, M, generator=gen, dtype=torch.float64))
     (Hc.real * G.real + Hc.imag * G.imag).sum().backward()
-    g_on, g_off = kspace.assemble_k_adjoint(G, g, kv, 0, n, 0, e, orank_all, nao)
+    g_on, g_off = kspace.assemble_k_adjoint(G, kspace.CrystalTables.from_graph(g, 0, n, 0, e, orank_all), kv)
     assert float((g_on - on.grad).abs().max()) < 1e-12 and float((g_off - off.grad).abs().max()) < 1e-12
     assert float(off.grad.abs().max()) > 0.1 and float((g_off.reshape(e, nao, nao)[:, 1, :].abs().sum(1) == 0).float().mean()) > 0   # masked orbitals

@@ -84,10 +84,16 @@ def hk_adjoint_numpy(G_, shift, kvec, pair_ptr, pair_edges, pair_ij, n_atoms, n_
     return g_on.reshape(n_atoms, nao * nao), g_off.reshape(n_edges, nao * nao)
 
 
-def _tables(case):
+def _tab(case, device="cpu"):
+    """the kspace.CrystalTables of the case's crystal"""
     from hamgnn_amd import kspace
     g, n0, n, e0, e, kv, nao, orank_all = case
-    return kspace._pair_tables(g, n0, n, e0, e, orank_all)
+    return kspace.CrystalTables.from_graph(g.to(device), n0, n, e0, e, orank_all.to(device))
+
+
+def _tables(case):
+    t = _tab(case)
+    return t.pair_ptr, t.pair_edges, t.pair_ij, t.orank, t.ooff, t.M
 
 
 def random_G(nk, M, seed=1, dtype=torch.float64):
@@ -98,8 +104,7 @@ def random_G(nk, M, seed=1, dtype=torch.float64):
 def reference_adjoint(case, G64):
     """the torch path of the adjoint in fp64 on the CPU"""
     from hamgnn_amd import kspace
-    g, n0, n, e0, e, kv, nao, orank_all = case
-    return kspace._assemble_k_adjoint_torch(G64, g, kv.double(), n0, n, e0, e, orank_all, nao)
+    return kspace._assemble_k_adjoint_torch(G64, _tab(case), case[5].double())      # (case[5]: its k-vectors)
 
 
 def absent_mask(case):
@@ -129,19 +134,18 @@ def check_adjoint_kernel(device, name, nk):
     ptr, order, pij, orank, ooff, M = _tables(case)
     G64 = random_G(nk, M)
     r_on, r_off = reference_adjoint(case, G64)
-    gd = g.to(device)
-    Gd, kvd, ord_ = G64.to(torch.complex64).to(device), kv.to(device), orank_all.to(device)
+    Gd, kvd = G64.to(torch.complex64).to(device), kv.to(device)
 
     def run():
-        t = kspace._pair_tables(gd, n0, n, e0, e, ord_)
-        return ops.hk_assemble_adjoint(Gd, gd.nbr_shift[e0:e0 + e].contiguous().float(), kvd, t[0], t[1], t[2], n, e, nao, t[3], t[4], t[5])
+        t = _tab(case, device)
+        return ops.hk_assemble_adjoint(Gd, t.shift, kvd, t.pair_ptr, t.pair_edges, t.pair_ij, n, e, nao, t.orank, t.ooff, t.M)
     a_on, a_off = run()
     b_on, b_off = run()
-    via_on, via_off = kspace.assemble_k_adjoint(Gd, gd, kvd, n0, n, e0, e, ord_, nao)      # the public entry: the kernel on a GPU tensor
+    via_on, via_off = kspace.assemble_k_adjoint(Gd, _tab(case, device), kvd)      # the public entry: the kernel on a GPU tensor
     prev = os.environ.get("HG_HK_ADJOINT")
     os.environ["HG_HK_ADJOINT"] = "torch"
     try:
-        t_on, t_off = kspace.assemble_k_adjoint(Gd, gd, kvd, n0, n, e0, e, ord_, nao)
+        t_on, t_off = kspace.assemble_k_adjoint(Gd, _tab(case, device), kvd)
     finally:
         os.environ.pop("HG_HK_ADJOINT") if prev is None else os.environ.__setitem__("HG_HK_ADJOINT", prev)
     m_on, m_off = absent_mask(case)
@@ -189,7 +193,7 @@ def check_adjoint_twin(name, nk, flip=False):
     g, n0, n, e0, e, kv, nao, orank_all = case
     ptr, order, pij, orank, ooff, M = _tables(case)
     G64 = random_G(nk, M)
-    r_on, r_off = kspace.assemble_k_adjoint(G64, g, kv.double(), n0, n, e0, e, orank_all, nao)
+    r_on, r_off = kspace.assemble_k_adjoint(G64, _tab(case), kv.double())
     orank = orank.clone()
     if flip:
         orank[0, int(torch.nonzero(orank[0] >= 0)[-1])] = -1
