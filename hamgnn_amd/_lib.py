@@ -26,7 +26,7 @@ EXPORTS = ["hg_last_error", "hg_version", "hg_scratch_bytes", "hg_edge_geometry"
            "hg_ham_finish", "hg_ham_readout", "hg_block_mean", "hg_soc_assemble", "hg_zero_point_shift", "hg_sym_contraction", "hg_sym_contraction3", "hg_sym_contraction_nu", "hg_sym_contraction_nu_backward", "hg_hk_assemble", "hg_hk_assemble_adjoint",
            "hg_attn_logits", "hg_attn_aggregate", "hg_linear_planar", "hg_linear_wgrad", "hg_block_gemm", "hg_gate_backward", "hg_radial_hidden_multi", "hg_mfma_probe", "hg_build_config", "hg_norm_act", "hg_norm_act_backward", "hg_w3_split_refill", "hg_kan_hidden",
            "hg_neighbour_bin", "hg_neighbour_pairs", "hg_neighbour_decode", "hg_mulliken_weights", "hg_dos_broaden", "hg_dos_tetra", "hg_bond_weights",
-           "hg_density_rows"]
+           "hg_density_rows", "hg_kgrad_elements"]
 
 
 def build(verbose=False):

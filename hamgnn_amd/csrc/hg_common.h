@@ -9,6 +9,11 @@ int hg_check_launch(const char* what);           // hipGetLastError() after a la
 
 struct HgWigOff { int o[8]; };                   // float offsets of D^l inside one packed Wigner row (host array -> kernarg)
 
+// Edge split of hg_kgrad_elements (spectra.hip; the size of its `part` scratch: hg_scratch_bytes in row_ops.hip): chunks of 8 ceil(E / 2048) edges, two per
+// wave at least and at most 256 chunks.  A function of the edge count alone, so that a pair's summation order does not depend on the launch it is in.
+static inline int64_t hg_kgrad_chunk_edges(int64_t E) { return 8 * ((E + 2047) / 2048 > 1 ? (E + 2047) / 2048 : 1); }
+static inline int64_t hg_kgrad_chunks(int64_t E) { return E > 0 ? (E + hg_kgrad_chunk_edges(E) - 1) / hg_kgrad_chunk_edges(E) : 0; }
+
 // The stream decides the device: an entry point runs its launches (and its one-time kernel-attribute calls) with the stream's device
 // current, so one host thread can drive several GPUs; the previous device is restored on exit.  The NULL stream means "current device".
 struct HgDeviceGuard {

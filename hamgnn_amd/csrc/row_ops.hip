@@ -31,7 +31,7 @@ extern "C" const char* hg_last_error(void) { return g_err; }
 extern "C" int hg_version(void) { return 2; }
 
 // Workspace query ("no hidden allocation on the hot path -- workspace size is queried").  No entry point of this library
-// allocates: outputs and scratch are caller-provided.  The two that need scratch beyond their documented outputs report its size here;
+// allocates: outputs and scratch are caller-provided.  Those that need scratch beyond their documented outputs report its size here;
 // every other entry point returns 0.  Host-only: callable without a GPU.
 extern "C" int64_t hg_scratch_bytes(const char* entry_point, int64_t rows, int arg) {
     if (!entry_point || rows < 0) return -1;
@@ -39,6 +39,7 @@ extern "C" int64_t hg_scratch_bytes(const char* entry_point, int64_t rows, int a
     if (is("hg_edge_geometry")) return rows * 4 * (int64_t)sizeof(float);              // ang_scratch [E][4]
     if (is("hg_zero_point_shift")) return 2 * (int64_t)(arg > 0 ? arg : 256) * (int64_t)sizeof(double);   // partial_scratch [2 nparts]
     if (is("hg_linear_wgrad")) return ((rows + 1023) / 1024) * (int64_t)(arg > 0 ? arg : 0) * 1024 * (int64_t)sizeof(float);   // partial [chunks][arg = nunits][16][64]
+    if (is("hg_kgrad_elements")) return hg_kgrad_chunks(arg) > 1 ? hg_kgrad_chunks(arg) * rows * 6 * (int64_t)sizeof(float) : 0;   // part [chunks(arg = n_edges)][rows = n_pairs][6]
     return 0;
 }
 

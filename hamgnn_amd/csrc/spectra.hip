@@ -4,6 +4,7 @@
 //   hg_dos_tetra:        the same GEMM with the linear tetrahedron method's corner weights (DOS or number of states) as the left operand
 //   hg_bond_weights:     per-state bond weights (COOP / COHP), w[s, g] = wk[s] * sum_{bonds of g} Re(phase c_i^+ X_bond c_j) from the real-space rows
 //   hg_density_rows:     the density matrix sampled on the rows of the crystal graph, P[e][a, b] = sum_s f_s Re(phase conj(c_ia) c_jb): an SDDMM over the states
+//   hg_kgrad_elements:   matrix elements of dX(k)/dk between pairs of states, out[p, alpha] = sum_e i rvec[e, alpha] phase c_bra^+ X_e c_ket: band velocities
 // No atomics, no claim-order reduction: all kernels are bit-reproducible from launch to launch.  Callers allocate everything.
 #include "hg_device.h"
 
@@ -386,15 +387,66 @@ extern "C" int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, in
 }
 
 // ------------------------------------------------------------------------------------------------ bond-resolved weights (COOP / COHP)
+// The contraction of one member (an edge or an on-site block) that bond_weights_kernel and kgrad_elements_kernel share, for the wave's 16 columns (column
+// lane & 15 = one pair of rows (cb, ck) of C; the same row twice for a bond weight): (pr, pi) = sum_{a, b} conj(cb[oi + ri[a]]) X[a][b] ck[oj + rj[b]].  T = X C_ket as two real GEMMs (X times Re and Im) on
+// v_mfma_f32_16x16x4_f32 over the nao x nao block as it lies in the row: row tiles of 16 orbitals a (NT of them, 2 NT independent accumulators), steps of 4
+// orbitals b; lane l holds A[a = 16 t + (l & 15)][b = 4 step + (l >> 4)] = X[a][b] and B[b][column l & 15].  Orbitals an atom does not have (rank < 0) and the
+// tails past nao go by predication: their A and B elements are 0 and nothing is read for them (the load is redirected to element 0 and its value dropped).
+// Then per lane sum_a conj(C_bra[a]) T[a] over its rows a = 16 t + 4 (l >> 4) + r (C/D map of the tile), and two shuffles add the four lane quarters: every
+// lane of a column ends with the column's sum.  Wave-uniform control flow: every lane reaches every MFMA and shuffle.
+template <int NT>
+__device__ __forceinline__ void member_contract(const float* __restrict__ X, const int32_t* __restrict__ ri, const int32_t* __restrict__ rj, int oi, int oj,
+                                                const float2* __restrict__ cb, const float2* __restrict__ ck, int nao, int M, int sl, int kq, float& pr_out,
+                                                float& pi_out) {
+    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
+    int ra[NT];                                            // rank of this lane's A row a = 16 t + sl, or -1
+    f32x4 tr[NT], ti[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int a = 16 * t + sl;
+        ra[t] = ri[a < nao ? a : 0];
+        ra[t] = a < nao ? ra[t] : -1;
+        tr[t] = f32x4{0.f, 0.f, 0.f, 0.f}, ti[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int b0 = 0; b0 < nao; b0 += 4) {
+        const int b = b0 + kq;
+        int rb = rj[b < nao ? b : 0];
+        rb = b < nao ? rb : -1;
+        float2 cj = ck[clampi(oj + rb, M)];
+        cj = rb >= 0 ? cj : make_float2(0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const bool ok = ra[t] >= 0 && rb >= 0;
+            float x = X[ok ? (16 * t + sl) * nao + b : 0];
+            x = ok ? x : 0.f;
+            tr[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.x, tr[t], 0, 0, 0);
+            ti[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.y, ti[t], 0, 0, 0);
+        }
+    }
+    float pr = 0.f, pi = 0.f;                              // sum_a conj(c_bra[a]) T[a] over this lane's rows: C/D map row = 4 (lane >> 4) + r, column of the wave
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int a = 16 * t + 4 * kq + r;
+            int rr = ri[a < nao ? a : 0];
+            rr = a < nao ? rr : -1;
+            float2 ci = cb[clampi(oi + rr, M)];
+            ci = rr >= 0 ? ci : make_float2(0.f, 0.f);
+            pr = fmaf(ci.y, ti[t][r], fmaf(ci.x, tr[t][r], pr));
+            pi = fmaf(-ci.y, tr[t][r], fmaf(ci.x, ti[t][r], pi));
+        }
+    pr += __shfl_xor(pr, 16, 64), pi += __shfl_xor(pi, 16, 64);
+    pr += __shfl_xor(pr, 32, 64), pi += __shfl_xor(pi, 32, 64);
+    pr_out = pr, pi_out = pi;
+}
+
 // W[s, 1 + g] = wk[s] * (sum_{e in edges(g)} t_e(s) + sum_{i in atoms(g)} o_i(s)),  t_e(s) = Re(exp(2 pi i k_s . shift_e) c_i^+ X_off[e] c_j), o_i(s) =
 // Re(c_i^+ X_on[i] c_i), (i, j) = (erow[e], ecol[e]) the row and column atom of hg_hk_assemble, c_i the entries ooff[i] + orank[i][a] of row s of C.
 // One workgroup owns one (tile of 16 states, group); the group's members -- its edges in the order of eidx, then its atoms in the order of aidx -- are
-// dealt to the 4 waves in contiguous quarters.  Per member a wave forms T = X C_j for its 16 states as two real GEMMs (X times Re C_j and Im C_j) on
-// v_mfma_f32_16x16x4_f32 over the nao x nao block as it lies in the row: row tiles of 16 orbitals a (NT of them, 2 NT independent accumulators), steps of 4
-// orbitals b; lane l holds A[a = 16 t + (l & 15)][b = 4 step + (l >> 4)] = X[a][b] and B[b][state l & 15] = C[s][ooff[j] + orank[j][b]].  Orbitals an atom
-// does not have (orank < 0) and the tails past nao go by predication: their A and B elements are 0 and nothing is read for them (the load is redirected
-// to element 0 and its value dropped), so rectangular blocks need no padded input.  Then per lane sum_a conj(C_i[a]) T[a] over its rows a = 16 t + 4 (l >> 4)
-// + r (C/D map of the tile), two shuffles add the four lane quarters, the phase (k . shift and sincos in double, rounded once, as hk_pairs_kernel) turns the
+// dealt to the 4 waves in contiguous quarters.  Per member a wave forms c_i^+ X c_j for its 16 states with member_contract (above: two real GEMMs on
+// v_mfma_f32_16x16x4_f32 over the nao x nao block as it lies in the row, missing orbitals and tails by predication, so rectangular blocks need no padded
+// input), the phase (k . shift and sincos in double, rounded once, as hk_pairs_kernel) turns the
 // complex sum into t_e, and the member is added to the wave's running sum.  The waves' sums are added through LDS as ((w0 + w1) + w2) + w3: one owner per
 // output element, a fixed order, no atomics.  The extra workgroups g = G write column 0 (= wk) and the pad columns (= 0); an empty group writes 0.  A state
 // row past ns repeats row ns - 1 and is not stored; the phase is per state, so the states of a tile may belong to different k-points, and a row of W does
@@ -452,45 +504,8 @@ __global__ __launch_bounds__(256) void bond_weights_kernel(const float2* __restr
         const int32_t* __restrict__ ri = orank + (int64_t)i * nao;
         const int32_t* __restrict__ rj = orank + (int64_t)j * nao;
         const int oi = ooff[i], oj = ooff[j];
-        int ra[NT];                                            // rank of this lane's A row a = 16 t + sl, or -1
-        f32x4 tr[NT], ti[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int a = 16 * t + sl;
-            ra[t] = ri[a < nao ? a : 0];
-            ra[t] = a < nao ? ra[t] : -1;
-            tr[t] = f32x4{0.f, 0.f, 0.f, 0.f}, ti[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        for (int b0 = 0; b0 < nao; b0 += 4) {
-            const int b = b0 + kq;
-            int rb = rj[b < nao ? b : 0];
-            rb = b < nao ? rb : -1;
-            float2 cj = c[clampi(oj + rb, M)];
-            cj = rb >= 0 ? cj : make_float2(0.f, 0.f);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bool ok = ra[t] >= 0 && rb >= 0;
-                float x = X[ok ? (16 * t + sl) * nao + b : 0];
-                x = ok ? x : 0.f;
-                tr[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.x, tr[t], 0, 0, 0);
-                ti[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, cj.y, ti[t], 0, 0, 0);
-            }
-        }
-        float pr = 0.f, pi = 0.f;                              // sum_a conj(c_i[a]) T[a] over this lane's rows: C/D map row = 4 (lane >> 4) + r, column = state
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int a = 16 * t + 4 * kq + r;
-                int rr = ri[a < nao ? a : 0];
-                rr = a < nao ? rr : -1;
-                float2 ci = c[clampi(oi + rr, M)];
-                ci = rr >= 0 ? ci : make_float2(0.f, 0.f);
-                pr = fmaf(ci.y, ti[t][r], fmaf(ci.x, tr[t][r], pr));
-                pi = fmaf(-ci.y, tr[t][r], fmaf(ci.x, ti[t][r], pi));
-            }
-        pr += __shfl_xor(pr, 16, 64), pi += __shfl_xor(pi, 16, 64);
-        pr += __shfl_xor(pr, 32, 64), pi += __shfl_xor(pi, 32, 64);
+        float pr, pi;
+        member_contract<NT>(X, ri, rj, oi, oj, c, c, nao, M, sl, kq, pr, pi);
         sum += fmaf(cf, pr, -(sf * pi));                       // Re(phase * sum); an on-site member has phase 1
     }
     if (kq == 0) part[wave][sl] = sum;
@@ -682,4 +697,113 @@ extern "C" int hg_density_rows(const float* C, int64_t ns, int M, const int32_t*
     else HG_DENSITY_LAUNCH(3);
 #undef HG_DENSITY_LAUNCH
     return hg_check_launch("hg_density_rows");
+}
+
+// ------------------------------------------------------------------------------------------------ k-gradient matrix elements (band velocities)
+// out[p, alpha] = sum_e i rvec[e, alpha] exp(2 pi i k_p . shift_e) sum_{a, b} conj(C[bra_p][mu(i, a)]) X_off[e][a, b] C[ket_p][mu(j, b)],  k_p the k-point of
+// state ket_p, (i, j) = (erow[e], ecol[e]) and mu(i, a) = ooff[i] + orank[i][a] as above: the element <bra| dX(k)/dk_alpha |ket> of the k-derivative of the
+// assembled matrix (its on-site blocks do not depend on k), without the M x M matrix.  The per-edge contraction is member_contract, the one of bond_weights_kernel, with two
+// rows of C: T = X C_ket as two real GEMMs on v_mfma_f32_16x16x4_f32 (row tiles of 16 orbitals, steps of 4, tails and missing orbitals by predication),
+// conj(C_bra) . T over the lane's rows in the C/D layout, two shuffles, then the phase (k . shift and sincos in double, rounded once) as a complex product
+// z_e, and per Cartesian component the running sums Re += -rvec z.im, Im += rvec z.re (one fused multiply-add each: a zero column of rvec gives exactly 0).
+// The single "group" is all E edges, so the edges are split: one workgroup owns one (tile of 16 pairs, chunk of hg_kgrad_chunk_edges(E) consecutive
+// edges); the chunk is dealt to the 4 waves in contiguous quarters, the waves' sums are added through LDS as ((w0 + w1) + w2) + w3 and stored to
+// part[chunk][pair][6] (or straight to out when there is one chunk).  kgrad_reduce_kernel then adds the chunks in ascending order: one owner per output
+// element, a fixed order, no atomics.  The chunk size depends on E alone, so a pair's bits depend neither on the launch's other pairs nor on their number;
+// a launch of one pair still spreads over ceil(E / chunk) workgroups.  A pair slot past n_pairs repeats pair n_pairs - 1 and is not stored.  Every table
+// entry (bra, ket, kidx, erow, ecol, orank / ooff) is clamped into range before it indexes anything.
+template <int NT>
+__global__ __launch_bounds__(256) void kgrad_elements_kernel(const float2* __restrict__ Cm, int ns, int M, const int32_t* __restrict__ bra,
+                                                             const int32_t* __restrict__ ket, int n_pairs, const int32_t* __restrict__ kidx,
+                                                             const float* __restrict__ kvec, int nk, const float* __restrict__ X_off,
+                                                             const int32_t* __restrict__ erow, const int32_t* __restrict__ ecol,
+                                                             const float* __restrict__ shift, const float* __restrict__ rvec, int E, int n_atoms, int nao,
+                                                             const int32_t* __restrict__ orank, const int32_t* __restrict__ ooff, int ntile, int chunk,
+                                                             float* __restrict__ dst) {
+    __shared__ float part[4][6][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ch = blockIdx.x / ntile, p0 = 16 * (blockIdx.x - ch * ntile);
+    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
+    const int sl = lane & 15, kq = lane >> 4;
+    const int pc = p0 + sl < n_pairs ? p0 + sl : n_pairs - 1;
+    const int sk = clampi(ket[pc], ns), sb = clampi(bra[pc], ns);
+    const float2* __restrict__ ck = Cm + (int64_t)sk * M;
+    const float2* __restrict__ cb = Cm + (int64_t)sb * M;
+    const int kp = clampi(kidx[sk], nk);
+    const double kx = kvec[3 * kp], ky = kvec[3 * kp + 1], kz = kvec[3 * kp + 2];
+    const int eb = ch * chunk, ee = eb + chunk < E ? eb + chunk : E;
+    const int quarter = (ee - eb + 3) >> 2;
+    const int m0 = eb + wave * quarter, m1 = m0 + quarter < ee ? m0 + quarter : ee;
+    const int nao2 = nao * nao;
+    float ar[3] = {0.f, 0.f, 0.f}, ai[3] = {0.f, 0.f, 0.f};
+    for (int e = m0; e < m1; ++e) {                            // (wave-uniform bounds and edge: every lane reaches every MFMA and shuffle)
+        const int i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+        const float* __restrict__ X = X_off + (int64_t)e * nao2;
+        // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
+        const double ph = 6.283185307179586 * (kx * shift[3 * (int64_t)e] + ky * shift[3 * (int64_t)e + 1] + kz * shift[3 * (int64_t)e + 2]);
+        double sd, cd;
+        sincos(ph, &sd, &cd);
+        const float cf = (float)cd, sf = (float)sd;
+        const int32_t* __restrict__ ri = orank + (int64_t)i * nao;
+        const int32_t* __restrict__ rj = orank + (int64_t)j * nao;
+        const int oi = ooff[i], oj = ooff[j];
+        float pr, pi;
+        member_contract<NT>(X, ri, rj, oi, oj, cb, ck, nao, M, sl, kq, pr, pi);
+        const float zr = fmaf(cf, pr, -(sf * pi)), zi = fmaf(cf, pi, sf * pr);      // z = phase * sum
+#pragma unroll
+        for (int al = 0; al < 3; ++al) {                       // i r z = -r z.im + i r z.re
+            const float r = rvec[3 * (int64_t)e + al];
+            ar[al] = fmaf(-r, zi, ar[al]), ai[al] = fmaf(r, zr, ai[al]);
+        }
+    }
+    if (kq == 0) {
+#pragma unroll
+        for (int al = 0; al < 3; ++al) part[wave][2 * al][sl] = ar[al], part[wave][2 * al + 1][sl] = ai[al];
+    }
+    __syncthreads();
+    if (threadIdx.x < 96) {                                    // 16 pairs x 6 floats, contiguous in dst
+        const int r = (int)threadIdx.x / 6, q = (int)threadIdx.x - 6 * r, p = p0 + r;
+        if (p < n_pairs) dst[((int64_t)ch * n_pairs + p) * 6 + q] = ((part[0][q][r] + part[1][q][r]) + part[2][q][r]) + part[3][q][r];
+    }
+}
+
+// out[x] = sum of part[c][x] over the chunks c in ascending order (x over the 6 n_pairs floats of out); no chunk (E = 0): zeros
+__global__ __launch_bounds__(256) void kgrad_reduce_kernel(const float* __restrict__ part, int64_t n, int nchunk, float* __restrict__ out) {
+    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= n) return;
+    float s = 0.f;
+    for (int c = 0; c < nchunk; ++c) s += part[(int64_t)c * n + x];
+    out[x] = s;
+}
+
+extern "C" int hg_kgrad_elements(const float* C, int64_t ns, int M, const int32_t* bra, const int32_t* ket, int64_t n_pairs, const int32_t* kidx,
+                                 const float* kvec, int nk, const float* X_off, const int32_t* erow, const int32_t* ecol, const float* shift,
+                                 const float* rvec, int64_t n_edges, int n_atoms, int nao, const int32_t* orank, const int32_t* ooff, float* part,
+                                 float* out, void* stream) {
+    HgDeviceGuard dev_guard(stream);
+    if (n_pairs <= 0) return 0;
+    const int64_t ntile = (n_pairs + 15) / 16;
+    if (ns <= 0 || ns > 2147483647LL || M <= 0 || nk <= 0 || n_atoms <= 0 || nao <= 0 || nao > 48 || n_edges < 0 || n_edges > 1073741824LL ||
+        n_pairs > (2147483647LL - 255) / 6 || ntile * hg_kgrad_chunks(n_edges) > 2147483647LL)
+        return hg_fail(-2, "hg_kgrad_elements: bad sizes (ns, M, nk, n_atoms >= 1, 1 <= nao <= 48, 0 <= n_edges <= 2^30, 6 n_pairs < 2^31 - 255, ceil(n_pairs / 16) chunks < 2^31)");
+    const int nchunk = (int)hg_kgrad_chunks(n_edges);
+    if (!C || !bra || !ket || !kidx || !kvec || !orank || !ooff || !out || (n_edges > 0 && (!X_off || !erow || !ecol || !shift || !rvec)) ||
+        (nchunk > 1 && !part))
+        return hg_fail(-2, "hg_kgrad_elements: null pointer");
+    if (nchunk > 0) {
+        const dim3 grid((unsigned)(ntile * nchunk));
+        float* dst = nchunk > 1 ? part : out;
+#define HG_KGRAD_LAUNCH(NT_)                                                                                                                              \
+    kgrad_elements_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, bra, ket, (int)n_pairs, kidx, kvec, nk, X_off, erow, ecol, \
+                                                                       shift, rvec, (int)n_edges, n_atoms, nao, orank, ooff, (int)ntile,                  \
+                                                                       (int)hg_kgrad_chunk_edges(n_edges), dst)
+        if (nao <= 16) HG_KGRAD_LAUNCH(1);
+        else if (nao <= 32) HG_KGRAD_LAUNCH(2);
+        else HG_KGRAD_LAUNCH(3);
+#undef HG_KGRAD_LAUNCH
+        if (nchunk == 1) return hg_check_launch("hg_kgrad_elements");
+    }
+    const int64_t n = 6 * n_pairs;
+    kgrad_reduce_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, (hipStream_t)stream>>>(part, n, nchunk, out);
+    return hg_check_launch("hg_kgrad_elements");
 }

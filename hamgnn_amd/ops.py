@@ -955,7 +955,7 @@ def bond_weights(C_, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, ep
 
 
 def check_state_tables(who, C_, kidx, kvec, erow, ecol, shift, orank, ooff, extra=()):
-    """The host checks the kernels on eigenvector rows share (hg_bond_weights, hg_density_rows; any device, so the torch paths run them too): C_ complex64
+    """The host checks the kernels on eigenvector rows share (hg_bond_weights, hg_density_rows, hg_kgrad_elements; any device, so the torch paths run them too): C_ complex64
     [ns, M]; kidx int32 [ns] -> rows of kvec fp32 [nk, 3]; erow / ecol int32 [E] -> atoms, shift fp32 [E, 3]; orank int32 [N, nao], ooff int32 [N] inside the
     M columns of C_.  extra: (name, tensor, shape, dtype) of the caller's further tensors, a shape entry either a number or one of "ns", "M", "N", "nao",
     "nao2", "E", "nk".  dtype, shape, device and contiguity of every tensor, then the index ranges (a device-to-host copy of two scalars each).  Each
@@ -1021,6 +1021,44 @@ def density_rows(C_, kidx, kvec, f, erow, ecol, shift, orank, ooff, out=None, ac
         raise ValueError("density_rows: C must be contiguous")
     call("hg_density_rows", torch.view_as_real(C_), ns, M, kidx, kvec, nk, f, erow, ecol, shift, E, N, nao, orank, ooff, bool(accumulate), P_on, P_off)
     return P_on, P_off
+
+
+def kgrad_elements_check(C_, bra, ket, kidx, kvec, X_off, erow, ecol, shift, rvec, orank, ooff):
+    """the host checks of kgrad_elements (any device; the torch path of hamgnn_amd/velocity.py runs them too): check_state_tables with the rows, rvec and the
+    pair lists, then bra / ket inside the states of C and both states of every pair at one k-point -> (ns, M, N, nao, E, nk, np)"""
+    for name, t in (("bra", bra), ("ket", ket)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"kgrad_elements: {name} must be int32 [np], got {tuple(getattr(t, 'shape', ()))}")
+    npair = int(bra.shape[0])
+    i32, f32 = torch.int32, torch.float32
+    ns, M, N, nao, E, nk = check_state_tables("kgrad_elements", C_, kidx, kvec, erow, ecol, shift, orank, ooff, extra=(
+        ("X_off", X_off, ("E", "nao2"), f32), ("rvec", rvec, ("E", 3), f32), ("bra", bra, (npair,), i32), ("ket", ket, (npair,), i32)))
+    for name, t in (("bra", bra), ("ket", ket)):
+        if npair and (int(t.min()) < 0 or int(t.max()) >= ns):
+            raise ValueError(f"kgrad_elements: {name} has entries outside the {ns} states of C")
+    if npair and bool((kidx[bra.long()] != kidx[ket.long()]).any()):
+        raise ValueError("kgrad_elements: bra and ket of a pair must lie at the same k-point (kidx[bra] != kidx[ket] somewhere)")
+    return ns, M, N, nao, E, nk, npair
+
+
+@_on_tensor_device
+def kgrad_elements(C_, bra, ket, kidx, kvec, X_off, erow, ecol, shift, rvec, orank, ooff):
+    """out [np, 3] complex64: out[p, alpha] = sum_e i rvec[e, alpha] phase_e(k_p) c_bra^+ X_off[e] c_ket, the elements of d X(k) / d k_alpha between the rows
+    bra[p] and ket[p] of C_ [ns, M] complex64 at the k-point kvec[kidx[ket[p]]] (see include/hamgnn_hip.h:hg_kgrad_elements).  bra / ket int32 [np]; kidx
+    int32 [ns] -> rows of kvec [nk, 3]; X_off [E, nao^2], rvec [E, 3] fp32; erow / ecol int32 [E], shift [E, 3]; orank int32 [N, nao], ooff int32 [N].  All
+    tables are checked here, on the host, before the launch.  The scratch of the edge split is allocated here, its size asked of the library."""
+    _require_gpu(C_)               # (the tables are read below, ahead of the launch)
+    ns, M, N, nao, E, nk, npair = kgrad_elements_check(C_, bra, ket, kidx, kvec, X_off, erow, ecol, shift, rvec, orank, ooff)
+    out = torch.empty(npair, 3, device=C_.device, dtype=torch.complex64)
+    if npair == 0:
+        return out
+    if not C_.is_contiguous():
+        raise ValueError("kgrad_elements: C must be contiguous")
+    nbytes = call("hg_scratch_bytes", b"hg_kgrad_elements", npair, E)
+    part = torch.empty(nbytes // 4, device=C_.device, dtype=torch.float32) if nbytes > 0 else None
+    call("hg_kgrad_elements", torch.view_as_real(C_), ns, M, bra, ket, npair, kidx, kvec, nk, X_off, erow, ecol, shift, rvec, E, N, nao, orank, ooff, part,
+         torch.view_as_real(out))
+    return out
 
 
 @_on_tensor_device

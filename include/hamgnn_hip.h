@@ -22,7 +22,8 @@ int hg_version(void);
 
 /* Workspace query.  No entry point of this library allocates or synchronises: every output and every scratch buffer is provided by
  * the caller (PyTorch's allocator in the shipped host code).  Scratch that is not an output: hg_edge_geometry (ang_scratch, rows = E)
- * and hg_zero_point_shift (partial_scratch, arg = nparts); all other entry points report 0.  Host-only, needs no GPU.
+ * hg_zero_point_shift (partial_scratch, arg = nparts) and hg_kgrad_elements (part, rows = n_pairs, arg = n_edges); all other entry points
+ * report 0.  Host-only, needs no GPU.
  * (SURVEY 8b sketched a plan-object ABI: plan create / workspace-bytes / forward-with-plan calls.  The built boundary keeps the
  * planner on the host side of the ABI instead: the C functions take the planner's tables as plain device arrays, so the library
  * holds no state, and this query stands in for the plan's workspace-bytes call.)                                                */
@@ -512,6 +513,28 @@ int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t* kidx, cons
 int hg_density_rows(const float* C, int64_t ns, int M, const int32_t* kidx, const float* kvec, int nk, const float* f, const int32_t* erow,
                     const int32_t* ecol, const float* shift, int64_t n_edges, int n_atoms, int nao, const int32_t* orank, const int32_t* ooff,
                     int accumulate, float* P_on, float* P_off, void* stream);
+
+/* Matrix elements of the k-derivative of an assembled matrix between pairs of states of one crystal (csrc/spectra.hip): band velocities by
+ * Hellmann-Feynman without an M x M matrix.  C, kidx, kvec, X_off, erow, ecol, shift, orank, ooff as hg_bond_weights.  bra, ket int32 [n_pairs]:
+ * rows of C; both states of a pair lie at the k-point of the ket, kvec[kidx[ket[p]]] (the caller checks kidx[bra[p]] == kidx[ket[p]]).
+ * rvec fp32 [n_edges][3]: the vector whose component alpha multiplies edge e -- the Cartesian lattice vector of the edge for d/dk in the
+ * gauge of hg_hk_assemble, plus the difference of the atoms' positions for the atomic gauge; its unit is the unit of the result.
+ *   out[p][alpha] = sum_e i rvec[e][alpha] exp(2 pi i k_p . shift[e]) sum_{a, b} conj(C[bra[p]][mu(i, a)]) X_off[e][a][b] C[ket[p]][mu(j, b)],
+ *   i = erow[e], j = ecol[e], sums over the orbitals both atoms have;  out complex64 [n_pairs][3] as (re, im) pairs.  The on-site blocks do not
+ *   depend on k and do not enter.  Every element of out is written; n_edges = 0 gives zeros, an all-zero column of rvec gives exactly 0.
+ * Per edge the contraction of hg_bond_weights (X C_ket as two real GEMMs on v_mfma_f32_16x16x4_f32, tails and missing orbitals by predication,
+ * conj(C_bra) . T in the C/D layout, the phase from k . shift and sincos in double, rounded once), then one fused multiply-add per component into
+ * the running sums.  One workgroup per (16 pairs, chunk of 8 ceil(n_edges / 2048) consecutive edges): the chunk goes to 4 waves in contiguous
+ * quarters, the waves add as ((w0 + w1) + w2) + w3 into part[chunk][pair][6], and a second launch adds the chunks in ascending order.  The chunk
+ * size depends on n_edges alone: a launch of one pair spreads over up to 256 workgroups, and a pair's result depends neither on the other pairs of
+ * the launch nor on their number.  No atomics: two launches are bit-identical.  part: fp32 scratch of hg_scratch_bytes("hg_kgrad_elements",
+ * n_pairs, n_edges) bytes (0, and part may be null, when the edges make one chunk or none).  Table entries are clamped into range before use; the
+ * caller checks them.  n_pairs <= 0: returns 0 without a launch.  Refused (-2): ns, M, nk or n_atoms < 1, ns >= 2^31, nao < 1 or > 48, n_edges < 0
+ * or > 2^30, 6 n_pairs >= 2^31 - 255, ceil(n_pairs / 16) chunks >= 2^31, a null pointer where the sizes are not empty.                          */
+int hg_kgrad_elements(const float* C, int64_t ns, int M, const int32_t* bra, const int32_t* ket, int64_t n_pairs, const int32_t* kidx,
+                      const float* kvec, int nk, const float* X_off, const int32_t* erow, const int32_t* ecol, const float* shift,
+                      const float* rvec, int64_t n_edges, int n_atoms, int nao, const int32_t* orank, const int32_t* ooff, float* part,
+                      float* out, void* stream);
 
 #ifdef __cplusplus
 }
