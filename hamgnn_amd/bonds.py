@@ -33,7 +33,7 @@ import torch
 
 from . import dos, ops
 from .basis import orbital_rank_table
-from .kspace import CrystalTables
+from .kspace import CrystalTables, edge_phases, padded_rows
 
 BY = ("edge", "pair", "species_pair")
 
@@ -141,13 +141,11 @@ def bond_tables(head, z, edge_index, nbr_shift, device):
 def _bond_weights_torch(C, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, ooff, eptr, eidx, aptr, aidx, wk, Gp, max_elems=1 << 24):
     """ops.bond_weights in torch ops: the rows of C gathered per atom into the nao-padded layout (0 where the atom lacks the orbital), then per chunk of
     group members one einsum c_i^+ X c_j, the phase (k . shift in double, rounded once), and index_add_ into the members' group columns"""
-    ns, M = C.shape
+    ns = int(C.shape[0])
     N, nao = orank.shape
     G = int(eptr.shape[0]) - 1
     dev = C.device
-    have = orank >= 0
-    comp = torch.where(have, ooff[:, None] + orank, torch.full_like(orank, M)).long()                # [N, nao]; M: the appended zero column
-    CA = torch.cat([C, C.new_zeros(ns, 1)], 1)[:, comp]                                               # [ns, N, nao]
+    CA, have = padded_rows(C, orank, ooff)                                                            # [ns, N, nao]
     W = torch.zeros(ns, Gp, device=dev, dtype=torch.float32)
     step = max(1, max_elems // max(1, ns * nao))
     hv = have.to(torch.float32)
@@ -160,8 +158,7 @@ def _bond_weights_torch(C, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, oo
             T = torch.einsum("eab,seb->sea", X.to(C.dtype), CA[:, j])
             p = (CA[:, i].conj() * T).sum(-1)                                                       # [ns, members]
             if phase:
-                ang = 2.0 * np.pi * (kvec.double()[kidx.long()] @ shift[m].double().T)            # [ns, members]
-                p = torch.complex(torch.cos(ang).float(), torch.sin(ang).float()) * p
+                p = edge_phases(kvec[kidx.long()], shift[m], torch.float32) * p                   # [ns, members]
             W.index_add_(1, 1 + gid[q0:q0 + step], p.real.contiguous())
 
     gid = lambda ptr_: torch.repeat_interleave(torch.arange(G, device=dev), (ptr_[1:] - ptr_[:-1]).long())
@@ -174,13 +171,17 @@ def _bond_weights_torch(C, kidx, kvec, X_on, X_off, erow, ecol, shift, orank, oo
     return W
 
 
+def group_tensors(groups, device):
+    """(eptr, eidx, aptr, aidx) of bond_groups(...) as int32 tensors on `device`; entries that are tensors already are taken as they are"""
+    return tuple(g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, dtype=np.int32)).to(device) for g in groups[:4])
+
+
 def bond_weights(C, kidx, kvec, X_on, X_off, tables, groups, wk, Gp):
     """W [ns, Gp] fp32 of the states whose eigenvector rows are C [ns, M] complex64 (kidx int32 [ns] -> rows of kvec fp32 [nk, 3]): column 0 = wk, column
     1 + g = wk * the weight of bond group g, pad columns 0, from the rows X_on [N, nao^2], X_off [E, nao^2] fp32 (overlap: COOP, Hamiltonian: COHP).
     tables: bond_tables(...) on C's device; groups: bond_groups(...) (numpy, or int32 tensors on C's device; the labels are not read); Gp from
     dos.padded_groups(G).  HIP kernel hg_bond_weights, or torch ops (see dos._use_kernels)."""
-    eptr, eidx, aptr, aidx = (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, dtype=np.int32)).to(C.device)
-                              for g in groups[:4])
+    eptr, eidx, aptr, aidx = group_tensors(groups, C.device)
     t = tables
     if int(C.shape[1]) != t.M:
         raise ValueError(f"bond_weights: C has {int(C.shape[1])} orbital columns, the tables {t.M}")

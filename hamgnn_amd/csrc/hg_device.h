@@ -1,5 +1,6 @@
 // hg_device.h -- device-side helpers shared by the kernels of libhamgnn_hip.so (gfx950): vector types, kernel-argument selects, LDS-DMA and
-// fp32 MFMA wrappers, segment flags of the edge programs, the HG_PROF phase profiler.  Included by every source that has a kernel.
+// fp32 MFMA wrappers, the index clamp and the Bloch phase of the k-space kernels, segment flags of the edge programs, the HG_PROF phase profiler.
+// Included by every source that has a kernel.
 #pragma once
 #include "hg_common.h"
 
@@ -29,6 +30,18 @@ __device__ __forceinline__ void hg_dma4(const float* __restrict__ gsrc, float* l
 }
 
 __device__ __forceinline__ f32x4 hg_mfma_f32_16x16x4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// v clamped into [0, n - 1]: what every entry of a caller's index table goes through before it indexes anything (spectra.hip)
+__device__ __forceinline__ int hg_clampi(int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; }
+
+// Bloch phase of an edge, (cos, sin) of 2 pi k . shift (kspace.hip, spectra.hip).  The angle and sincos in double, rounded to fp32 once: |k . shift|
+// reaches tens of turns for long bonds, and sincosf loses the fraction.
+__device__ __forceinline__ float2 hg_edge_phase(double kx, double ky, double kz, double sx, double sy, double sz) {
+    const double ph = 6.283185307179586 * (kx * sx + ky * sy + kz * sz);
+    double sd, cd;
+    sincos(ph, &sd, &cd);
+    return make_float2((float)cd, (float)sd);
+}
 
 // segment flags of the edge programs (tp_fused.hip, tp_is.hip; plan/program.py)
 #define SEG_UNROTATE 1

@@ -40,13 +40,10 @@ __global__ __launch_bounds__(256) void hk_pairs_kernel(const float* __restrict__
         float re = 0.f, im = 0.f;
         for (int64_t t = q0; t < q1; ++t) {
             const int64_t e = pair_edges[t];
-            // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
-            const double ph = 6.283185307179586 * ((double)kx * shift[3 * e] + (double)ky * shift[3 * e + 1] + (double)kz * shift[3 * e + 2]);
-            double s, c;
-            sincos(ph, &s, &c);
+            const float2 cs = hg_edge_phase(kx, ky, kz, shift[3 * e], shift[3 * e + 1], shift[3 * e + 2]);
             const float h = off[e * nao2 + q];
-            re = fmaf((float)c, h, re);
-            im = fmaf((float)s, h, im);
+            re = fmaf(cs.x, h, re);
+            im = fmaf(cs.y, h, im);
         }
         float2* dst = Hk + ((int64_t)k * M + ooff[i] + ra) * M + ooff[j] + rb;
         const float2 old = *dst;                               // (i, i) pairs (self images) add onto the on-site block; one owner per element
@@ -133,11 +130,7 @@ __global__ __launch_bounds__(256) void hk_adj_pairs_kernel(const float2* __restr
                 const double kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
                 for (int x = 0; x < ec; ++x) {
                     const int64_t e = pair_edges[t0 + x];
-                    // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
-                    const double a_ = 6.283185307179586 * (kx * shift[3 * e] + ky * shift[3 * e + 1] + kz * shift[3 * e + 2]);
-                    double s, c;
-                    sincos(a_, &s, &c);
-                    ph[x][threadIdx.x] = make_float2((float)c, (float)s);
+                    ph[x][threadIdx.x] = hg_edge_phase(kx, ky, kz, shift[3 * e], shift[3 * e + 1], shift[3 * e + 2]);
                 }
             }
             __syncthreads();

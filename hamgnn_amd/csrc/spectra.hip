@@ -46,29 +46,106 @@ extern "C" int hg_mulliken_weights(const float* C, const float* SC, int64_t ns, 
     return hg_check_launch("hg_mulliken_weights");
 }
 
-// ------------------------------------------------------------------------------------------------ Gaussian broadening
-// One workgroup owns one (tile of 16 energies, slab of DB_NT * 16 group columns).  The states that matter to the tile are a contiguous window of
-// the ascending eps: [first eps >= E_first - 6 sigma, last eps <= E_last + 6 sigma], found by two binary searches.  The window is cut into steps
-// of 4 states (one v_mfma_f32_16x16x4_f32 each) and the steps are dealt to the 4 waves in contiguous quarters.  Per step a lane generates ONE
-// element of the A fragment, A[energy lane & 15][state lane >> 4] = norm * exp(-((E - eps) / sigma)^2 / 2) -- the difference and the exponent in
-// double, rounded to fp32 once, so the Gaussian's argument carries half an ulp -- and loads one element of W per 16-column accumulator; the A
-// fragment is reused across the DB_NT accumulators.  Accumulator t holds the slab's columns DB_NT * i + t (i = lane & 15 its MFMA column), so a
-// lane's DB_NT elements of W are adjacent: one 16-byte load per lane and step, a whole 256-byte row segment per 16 lanes, and one 16-byte store per
-// lane and output row (Gp a multiple of 4, as dos.py pads it; any other Gp takes element loads).  The waves' partial tiles are added through LDS
-// in the order ((w0 + w1) + w2) + w3.
-// Tails by predication: a state slot past the window contributes a Gaussian of 0, a column >= Gp is never stored, and neither is read (their loads are
-// clamped onto the window's last state / the row's last columns); rows >= ne are computed and dropped.
+// ------------------------------------------------------------------------------------------------ the tile of the two DOS GEMMs
+// D[j, g] = sum_s A[j, s] W[s, g]: dos_broaden_kernel and dos_tetra_kernel differ in the window of states and in how a lane generates its element of A;
+// the rest is here.  One workgroup owns one (tile of 16 energies, slab of DB_NT * 16 group columns).  The states that matter to the tile are cut into
+// steps of 4 (one v_mfma_f32_16x16x4_f32 each: lane l holds A[energy l & 15][state l >> 4]) and the steps are dealt to the 4 waves in contiguous quarters.
+// Per step a lane loads one element of W per 16-column accumulator; the A fragment is reused across the DB_NT accumulators.  Accumulator t holds the
+// slab's columns DB_NT * i + t (i = lane & 15 its MFMA column), so a lane's DB_NT elements of W are adjacent: one 16-byte load per lane and step, a whole
+// 256-byte row segment per 16 lanes, and one 16-byte store per lane and output row (VEC: Gp a multiple of 4, as dos.py pads it, rows of W and D 16-byte
+// aligned; any other Gp takes element loads and stores).  C/D map of a 16x16 tile: MFMA column = lane & 15, row = 4 (lane >> 4) + r.  The waves' partial
+// tiles are added through LDS in the order ((w0 + w1) + w2) + w3; wave w adds and stores the rows r = w.
+// Tails by predication: a state slot past the window contributes an A element of 0, a column >= Gp is never stored, and neither is read (their loads are
+// clamped onto the window's last state / the row's last columns, always inside W); rows >= ne are computed and dropped.
 #define DB_NT 4                                              // 16-column accumulators per wave: 4 independent MFMA chains cover the 40-cycle latency
 #define DB_WAVES 4                                           // = the 4 result registers of a lane: wave w reduces and stores register w
-#define DB_BLK 16                                            // steps per block: 64 states, one eigenvalue per lane
 static_assert(DB_NT == 4, "a lane's columns are one float4");
-template <bool VEC>                                          // VEC: Gp a multiple of 4, rows of W and D are 16-byte aligned: a lane's columns are one float4
+struct DosTile {
+    int lane, wave, sl, kq;                                  // sl = lane & 15: the lane's energy of a step and its MFMA column; kq = lane >> 4: its state of a step, its row quarter
+    int j0, col, colc;                                       // first energy of the tile; first of the lane's DB_NT adjacent columns; the same clamped for VEC loads
+};
+template <bool VEC>
+__device__ __forceinline__ DosTile dos_tile(int Gp) {
+    DosTile t;
+    t.lane = threadIdx.x & 63, t.wave = threadIdx.x >> 6, t.sl = t.lane & 15, t.kq = t.lane >> 4;
+    t.j0 = blockIdx.x * 16, t.col = blockIdx.y * (16 * DB_NT) + DB_NT * t.sl;
+    t.colc = VEC ? (t.col < Gp ? t.col : Gp - DB_NT) : 0;
+    return t;
+}
+// the steps [st0, st1) of this wave: contiguous quarters of the nsteps (wave-uniform)
+__device__ __forceinline__ void dos_wave_steps(const DosTile& t, int nsteps, int& st0, int& st1) {
+    const int chunk = (nsteps + DB_WAVES - 1) / DB_WAVES;
+    st0 = t.wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
+}
+// the lane's DB_NT columns of the row w of W
+template <bool VEC>
+__device__ __forceinline__ void dos_load_w(const float* __restrict__ w, const DosTile& t, int Gp, float (&bv)[DB_NT]) {
+    if (VEC) {
+        const float4 v = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w + t.colc, 16));
+        bv[0] = v.x, bv[1] = v.y, bv[2] = v.z, bv[3] = v.w;
+    } else {
+#pragma unroll
+        for (int c = 0; c < DB_NT; ++c) bv[c] = w[t.col + c < Gp ? t.col + c : Gp - 1];
+    }
+}
+// the waves' partial tiles to LDS, their sum in the fixed order, the store (accumulate: added to what D holds)
+template <bool VEC>
+__device__ __forceinline__ void dos_epilogue(const f32x4 (&acc)[DB_NT], const DosTile& t, int ne, int Gp, int accumulate, float* __restrict__ D) {
+    __shared__ float part[DB_WAVES][DB_NT][4][64];
+#pragma unroll
+    for (int c = 0; c < DB_NT; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[t.wave][c][r][t.lane] = acc[c][r];
+    __syncthreads();
+    const int r = t.wave, row = t.j0 + 4 * t.kq + r;
+    float v[DB_NT];
+#pragma unroll
+    for (int c = 0; c < DB_NT; ++c) {
+        v[c] = part[0][c][r][t.lane];
+#pragma unroll
+        for (int w2 = 1; w2 < DB_WAVES; ++w2) v[c] += part[w2][c][r][t.lane];
+    }
+    if (row >= ne) return;
+    float* dst = D + (int64_t)row * Gp + t.col;
+    if (VEC) {
+        if (t.col < Gp) {
+            float4 o = make_float4(v[0], v[1], v[2], v[3]);
+            if (accumulate) {
+                const float4 old = *reinterpret_cast<const float4*>(dst);
+                o = make_float4(old.x + o.x, old.y + o.y, old.z + o.z, old.w + o.w);
+            }
+            *reinterpret_cast<float4*>(dst) = o;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < DB_NT; ++c)
+            if (t.col + c < Gp) dst[c] = accumulate ? dst[c] + v[c] : v[c];
+    }
+}
+// grid of both kernels: energy tiles on x, column slabs on y; false where the slabs exceed the grid's y limit
+static bool dos_grid(int ne, int Gp, dim3& grid) {
+    grid = dim3((unsigned)((ne + 15) / 16), (unsigned)((Gp + 16 * DB_NT - 1) / (16 * DB_NT)));
+    return grid.y <= 65535u;
+}
+// launch of kernel_<VEC>: VEC where the rows of W and D can be read as float4
+#define HG_DOS_LAUNCH(kernel_, Gp_, grid_, stream_, ...)                                                       \
+    do {                                                                                                       \
+        if (((Gp_) & 3) == 0) kernel_<true><<<grid_, 64 * DB_WAVES, 0, (hipStream_t)(stream_)>>>(__VA_ARGS__); \
+        else kernel_<false><<<grid_, 64 * DB_WAVES, 0, (hipStream_t)(stream_)>>>(__VA_ARGS__);                 \
+    } while (0)
+
+// ------------------------------------------------------------------------------------------------ Gaussian broadening
+// The tile, the W loads, the tails and the epilogue are the DOS tile's (above).  The states that matter to the tile are a contiguous window of the
+// ascending eps: [first eps >= E_first - 6 sigma, last eps <= E_last + 6 sigma], found by two binary searches.  Per step a lane generates ONE element of
+// the A fragment, A[energy lane & 15][state lane >> 4] = norm * exp(-((E - eps) / sigma)^2 / 2) -- the difference and the exponent in double, rounded to
+// fp32 once, so the Gaussian's argument carries half an ulp.
+#define DB_BLK 16                                            // steps per block: 64 states, one eigenvalue per lane
+template <bool VEC>
 __global__ __launch_bounds__(64 * DB_WAVES) void dos_broaden_kernel(const float* __restrict__ eps, const float* __restrict__ W, int ns, int Gp, double E0,
                                                                     double dE, int ne, double inv_sigma, float norm, double cut, int accumulate,
                                                                     float* __restrict__ D) {
-    __shared__ float part[DB_WAVES][DB_NT][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j0 = blockIdx.x * 16, c0 = blockIdx.y * (16 * DB_NT);
+    const DosTile tl = dos_tile<VEC>(Gp);
+    const int lane = tl.lane, kq = tl.kq, j0 = tl.j0;
     const int jl = j0 + 15 < ne ? j0 + 15 : ne - 1;
     const double lo = E0 + (double)j0 * dE - cut, hi = E0 + (double)jl * dE + cut;
     int a = 0, b = ns;
@@ -85,29 +162,17 @@ __global__ __launch_bounds__(64 * DB_WAVES) void dos_broaden_kernel(const float*
     const int s_hi = a;
     const int nsteps = (s_hi - s_lo + 3) >> 2;
     if (nsteps == 0 && accumulate) return;                     // (block-uniform) an empty window leaves D alone
-    const int chunk = (nsteps + DB_WAVES - 1) / DB_WAVES;
-    const int st0 = wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
+    int st0, st1;
+    dos_wave_steps(tl, nsteps, st0, st1);
     const double Ej = E0 + (double)(j0 + (lane & 15)) * dE;
-    const int kq = lane >> 4, col = c0 + DB_NT * (lane & 15);   // first of this lane's DB_NT adjacent columns
-    f32x4 acc[DB_NT];
-#pragma unroll
-    for (int t = 0; t < DB_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // one step = this lane's state s = s_lo + 4 st + kq: its eigenvalue and its DB_NT elements of W.  No branch around a load: a state slot past the
-    // window reads the window's last state and a column past Gp the row's last ones (always inside W), the slot's Gaussian is set to 0 and columns
-    // >= Gp are never stored.  Steps go in blocks of DB_BLK: the block's 4 DB_BLK eigenvalues are ONE coalesced load (lane l: state 4 sb + l) handed
-    // round by a lane shuffle, and the block's W loads are all requested before its first Gaussian is formed.
-    const int colc = VEC ? (col < Gp ? col : Gp - DB_NT) : 0;
+    f32x4 acc[DB_NT] = {};
+    // one step = this lane's state s = s_lo + 4 st + kq: its eigenvalue and its DB_NT elements of W.  No branch around a load (the tile's tails).  Steps
+    // go in blocks of DB_BLK: the block's 4 DB_BLK eigenvalues are ONE coalesced load (lane l: state 4 sb + l) handed round by a lane shuffle, and the
+    // block's W loads are all requested before its first Gaussian is formed.
     auto load_w = [&](int st, float (&bv)[DB_NT]) {
         int s = s_lo + 4 * st + kq;
         s = s < s_hi ? s : s_hi - 1;
-        const float* __restrict__ w = W + (int64_t)s * Gp;
-        if (VEC) {
-            const float4 v = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w + colc, 16));
-            bv[0] = v.x, bv[1] = v.y, bv[2] = v.z, bv[3] = v.w;
-        } else {
-#pragma unroll
-            for (int t = 0; t < DB_NT; ++t) bv[t] = w[col + t < Gp ? col + t : Gp - 1];
-        }
+        dos_load_w<VEC>(W + (int64_t)s * Gp, tl, Gp, bv);
     };
     auto load_eps = [&](int sb) {
         const int s = s_lo + 4 * sb + lane;
@@ -137,38 +202,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void dos_broaden_kernel(const float*
             step(sb + i, __shfl(e64, 4 * i + kq, 64), bv);
         }
     }
-#pragma unroll
-    for (int t = 0; t < DB_NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[wave][t][r][lane] = acc[t][r];
-    __syncthreads();
-    {                                                          // C/D map of a 16x16 tile: MFMA column = lane & 15, row = 4 (lane >> 4) + r; wave w adds and stores rows r = w
-        const int r = wave, row = j0 + 4 * kq + r;
-        float v[DB_NT];
-#pragma unroll
-        for (int t = 0; t < DB_NT; ++t) {
-            v[t] = part[0][t][r][lane];
-#pragma unroll
-            for (int w2 = 1; w2 < DB_WAVES; ++w2) v[t] += part[w2][t][r][lane];
-        }
-        if (row < ne) {
-            float* dst = D + (int64_t)row * Gp + col;
-            if (VEC) {
-                if (col < Gp) {
-                    float4 o = make_float4(v[0], v[1], v[2], v[3]);
-                    if (accumulate) {
-                        const float4 old = *reinterpret_cast<const float4*>(dst);
-                        o = make_float4(old.x + o.x, old.y + o.y, old.z + o.z, old.w + o.w);
-                    }
-                    *reinterpret_cast<float4*>(dst) = o;
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < DB_NT; ++t)
-                    if (col + t < Gp) dst[t] = accumulate ? dst[t] + v[t] : v[t];
-            }
-        }
-    }
+    dos_epilogue<VEC>(acc, tl, ne, Gp, accumulate, D);
 }
 
 extern "C" int hg_dos_broaden(const float* eps, const float* W, int64_t ns, int Gp, double E0, double dE, int ne, double sigma, int accumulate,
@@ -177,15 +211,10 @@ extern "C" int hg_dos_broaden(const float* eps, const float* W, int64_t ns, int 
     if (ne <= 0 || Gp <= 0) return 0;
     if (!(sigma > 0.0) || !(dE > 0.0) || ns < 0 || ns > 2147483647LL - 8 || !D || (ns > 0 && (!eps || !W)) || (((uintptr_t)W | (uintptr_t)D) & 15))
         return hg_fail(-2, "hg_dos_broaden: bad arguments (sigma and dE must be positive, ns < 2^31, W and D 16-byte aligned)");
-    const unsigned gx = (unsigned)((ne + 15) / 16), gy = (unsigned)((Gp + 16 * DB_NT - 1) / (16 * DB_NT));
-    if (gy > 65535u) return hg_fail(-2, "hg_dos_broaden: too many group columns");
+    dim3 grid;
+    if (!dos_grid(ne, Gp, grid)) return hg_fail(-2, "hg_dos_broaden: too many group columns");
     const float norm = (float)(1.0 / (sigma * 2.5066282746310002));      // 1 / (sigma sqrt(2 pi))
-    if ((Gp & 3) == 0)
-        dos_broaden_kernel<true><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, (int)ns, Gp, E0, dE, ne, 1.0 / sigma, norm, 6.0 * sigma,
-                                                                                           accumulate ? 1 : 0, D);
-    else
-        dos_broaden_kernel<false><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, (int)ns, Gp, E0, dE, ne, 1.0 / sigma, norm, 6.0 * sigma,
-                                                                                            accumulate ? 1 : 0, D);
+    HG_DOS_LAUNCH(dos_broaden_kernel, Gp, grid, stream, eps, W, (int)ns, Gp, E0, dE, ne, 1.0 / sigma, norm, 6.0 * sigma, accumulate ? 1 : 0, D);
     return hg_check_launch("hg_dos_broaden");
 }
 
@@ -245,7 +274,7 @@ __device__ __forceinline__ double tetra_corner(double e1, double e2, double e3, 
                   : ((D1 + D2 + D3) * a + (C1 + C2 + C3)) * i41 + (D3 * b + C3) * i42;
 }
 
-// One workgroup owns one (tile of 16 energies, slab of 64 columns), as dos_broaden_kernel, and the GEMM runs over the states s = (band, k).  eps ascends
+// The tile, the W loads, the tails and the epilogue are the DOS tile's (above), and the GEMM runs over the states s = (band, k).  eps ascends
 // in b at every k, so band_lo (min over k) and band_hi (max over k) both ascend in b and the bands that matter to the tile are a contiguous range found
 // by binary search: DOS -- band_hi >= E_first - 2 dE and band_lo <= E_last + 2 dE (a tetrahedron contributes inside [e1, e4], a flat one within dE of
 // its mean; the second dE keeps a rounding of the limit out of the decision); number of states -- band_lo <= E_last, and the bands with band_hi <=
@@ -254,17 +283,16 @@ __device__ __forceinline__ double tetra_corner(double e1, double e2, double e3, 
 // quarters.  Per step a lane generates ONE element A[energy lane & 15][state lane >> 4]: it walks the corner table of its k-row in the table's order
 // (ascending tetrahedron: the fixed summation order), per entry loads the tetrahedron's four eigenvalues of band b, sorts them (5 comparators), takes
 // the rank of its own corner (ties: the lower slot first, so repeated corners of a folded or n_i = 1 grid take distinct ranks) and adds tetra_corner
-// in double; the sum is rounded to fp32 once.  The 16 lanes of a state walk the same entries: their loads are one address.  W loads, tails, the
-// LDS reduction ((w0 + w1) + w2) + w3 and the stores are dos_broaden_kernel's.  Table entries are clamped into range before they index anything.
+// in double; the sum is rounded to fp32 once.  The 16 lanes of a state walk the same entries: their loads are one address.  Table entries are clamped
+// into range before they index anything.
 template <bool VEC>
 __global__ __launch_bounds__(64 * DB_WAVES) void dos_tetra_kernel(const float* __restrict__ eps, const float* __restrict__ W, int nk, int nb, int Gp,
                                                                   const int4* __restrict__ tet, int nt, const int32_t* __restrict__ kt_ptr,
                                                                   const int32_t* __restrict__ kt_tet, const int32_t* __restrict__ kt_corner,
                                                                   const float* __restrict__ band_lo, const float* __restrict__ band_hi, double E0,
                                                                   double dE, int ne, int mode, int accumulate, float* __restrict__ D) {
-    __shared__ float part[DB_WAVES][DB_NT][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j0 = blockIdx.x * 16, c0 = blockIdx.y * (16 * DB_NT);
+    const DosTile tl = dos_tile<VEC>(Gp);
+    const int lane = tl.lane, kq = tl.kq, j0 = tl.j0;
     const int jl = j0 + 15 < ne ? j0 + 15 : ne - 1;
     auto energy = [&](int j) { return __dadd_rn(E0, __dmul_rn((double)j, dE)); };      // (two roundings, as the host computes the grid: no fma)
     const double E_first = energy(j0), E_last = energy(jl), g_lo = E0, g_hi = energy(ne - 1);
@@ -282,37 +310,24 @@ __global__ __launch_bounds__(64 * DB_WAVES) void dos_tetra_kernel(const float* _
     const int ns = b_hi > b_lo ? (b_hi - b_lo) * nk : 0;                                 // (the host keeps nk nb below 2^31)
     const int nsteps = (ns + 3) >> 2;
     if (nsteps == 0 && accumulate) return;                     // (block-uniform) no band in reach leaves D alone
-    const int chunk = (nsteps + DB_WAVES - 1) / DB_WAVES;
-    const int st0 = wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
-    const double Ej = energy(j0 + (lane & 15)), v = 1.0 / (double)nt;
-    const int kq = lane >> 4, col = c0 + DB_NT * (lane & 15);
-    const int colc = VEC ? (col < Gp ? col : Gp - DB_NT) : 0;
-    f32x4 acc[DB_NT];
-#pragma unroll
-    for (int t = 0; t < DB_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int st0, st1;
+    dos_wave_steps(tl, nsteps, st0, st1);
+    const double Ej = energy(j0 + tl.sl), v = 1.0 / (double)nt;
+    f32x4 acc[DB_NT] = {};
     for (int st = st0; st < st1; ++st) {                       // (wave-uniform bounds; st0 < st1 implies ns > 0)
         const int s_raw = 4 * st + kq, s = s_raw < ns ? s_raw : ns - 1;
         const int bb = s / nk, k = s - bb * nk, b = b_lo + bb;
-        const float* __restrict__ w = W + ((int64_t)k * nb + b) * Gp;
         float bv[DB_NT];
-        if (VEC) {
-            const float4 x = *reinterpret_cast<const float4*>(__builtin_assume_aligned(w + colc, 16));
-            bv[0] = x.x, bv[1] = x.y, bv[2] = x.z, bv[3] = x.w;
-        } else {
-#pragma unroll
-            for (int t = 0; t < DB_NT; ++t) bv[t] = w[col + t < Gp ? col + t : Gp - 1];
-        }
+        dos_load_w<VEC>(W + ((int64_t)k * nb + b) * Gp, tl, Gp, bv);
         const int q0 = kt_ptr[k] > 0 ? kt_ptr[k] : 0, q1 = kt_ptr[k + 1] < 4 * nt ? kt_ptr[k + 1] : 4 * nt;
         double A = 0.0;
         if (b < b_full) {
             A = (double)(q1 - q0) * (0.25 * v);
         } else {
             for (int q = q0; q < q1; ++q) {
-                int T = kt_tet[q];
-                T = T < 0 ? 0 : T < nt ? T : nt - 1;
                 const int slot = kt_corner[q] & 3;
-                const int4 cn = tet[T];
-                auto ev = [&](int kk) { kk = kk < 0 ? 0 : kk < nk ? kk : nk - 1; return (double)eps[(int64_t)kk * nb + b]; };
+                const int4 cn = tet[hg_clampi(kt_tet[q], nt)];
+                auto ev = [&](int kk) { return (double)eps[(int64_t)hg_clampi(kk, nk) * nb + b]; };
                 double x0 = ev(cn.x), x1 = ev(cn.y), x2 = ev(cn.z), x3 = ev(cn.w);
                 const double me = slot == 0 ? x0 : slot == 1 ? x1 : slot == 2 ? x2 : x3;
                 const int r = (int)(x0 < me || (x0 == me && 0 < slot)) + (int)(x1 < me || (x1 == me && 1 < slot)) +
@@ -328,38 +343,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void dos_tetra_kernel(const float* _
 #pragma unroll
         for (int t = 0; t < DB_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[t], acc[t], 0, 0, 0);
     }
-#pragma unroll
-    for (int t = 0; t < DB_NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[wave][t][r][lane] = acc[t][r];
-    __syncthreads();
-    {                                                          // C/D map of a 16x16 tile: MFMA column = lane & 15, row = 4 (lane >> 4) + r; wave w adds and stores rows r = w
-        const int r = wave, row = j0 + 4 * kq + r;
-        float o[DB_NT];
-#pragma unroll
-        for (int t = 0; t < DB_NT; ++t) {
-            o[t] = part[0][t][r][lane];
-#pragma unroll
-            for (int w2 = 1; w2 < DB_WAVES; ++w2) o[t] += part[w2][t][r][lane];
-        }
-        if (row < ne) {
-            float* dst = D + (int64_t)row * Gp + col;
-            if (VEC) {
-                if (col < Gp) {
-                    float4 x = make_float4(o[0], o[1], o[2], o[3]);
-                    if (accumulate) {
-                        const float4 old = *reinterpret_cast<const float4*>(dst);
-                        x = make_float4(old.x + x.x, old.y + x.y, old.z + x.z, old.w + x.w);
-                    }
-                    *reinterpret_cast<float4*>(dst) = x;
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < DB_NT; ++t)
-                    if (col + t < Gp) dst[t] = accumulate ? dst[t] + o[t] : o[t];
-            }
-        }
-    }
+    dos_epilogue<VEC>(acc, tl, ne, Gp, accumulate, D);
 }
 
 extern "C" int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, int Gp, const int32_t* tet, int64_t nt, const int32_t* kt_ptr,
@@ -374,17 +358,22 @@ extern "C" int hg_dos_tetra(const float* eps, const float* W, int nk, int nb, in
     if (!D || (states && (!eps || !W || !tet || !kt_ptr || !kt_tet || !kt_corner || !band_lo || !band_hi)))
         return hg_fail(-2, "hg_dos_tetra: null pointer");
     if ((((uintptr_t)W | (uintptr_t)D | (uintptr_t)tet) & 15)) return hg_fail(-2, "hg_dos_tetra: W, D and tet must be 16-byte aligned");
-    const unsigned gx = (unsigned)((ne + 15) / 16), gy = (unsigned)((Gp + 16 * DB_NT - 1) / (16 * DB_NT));
-    if (gy > 65535u) return hg_fail(-2, "hg_dos_tetra: too many group columns");
+    dim3 grid;
+    if (!dos_grid(ne, Gp, grid)) return hg_fail(-2, "hg_dos_tetra: too many group columns");
     const int nbe = states ? nb : 0;                           // no band in reach of any tile: zeros written / D left alone, nothing read
-    if ((Gp & 3) == 0)
-        dos_tetra_kernel<true><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner,
-                                                                                         band_lo, band_hi, E0, dE, ne, mode, accumulate ? 1 : 0, D);
-    else
-        dos_tetra_kernel<false><<<dim3(gx, gy), 64 * DB_WAVES, 0, (hipStream_t)stream>>>(eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner,
-                                                                                          band_lo, band_hi, E0, dE, ne, mode, accumulate ? 1 : 0, D);
+    HG_DOS_LAUNCH(dos_tetra_kernel, Gp, grid, stream, eps, W, nk, nbe, Gp, (const int4*)tet, (int)nt, kt_ptr, kt_tet, kt_corner, band_lo, band_hi, E0, dE, ne, mode,
+                  accumulate ? 1 : 0, D);
     return hg_check_launch("hg_dos_tetra");
 }
+
+// ------------------------------------------------------------------------------------------------ kernels on rows of eigenvectors
+// launch of kernel_<NT> (256 threads), NT = the 16-orbital tiles that cover nao <= 48
+#define HG_NT_LAUNCH(kernel_, nao_, grid_, stream_, ...)                                                  \
+    do {                                                                                                  \
+        if ((nao_) <= 16) kernel_<1><<<grid_, 256, 0, (hipStream_t)(stream_)>>>(__VA_ARGS__);             \
+        else if ((nao_) <= 32) kernel_<2><<<grid_, 256, 0, (hipStream_t)(stream_)>>>(__VA_ARGS__);        \
+        else kernel_<3><<<grid_, 256, 0, (hipStream_t)(stream_)>>>(__VA_ARGS__);                          \
+    } while (0)
 
 // ------------------------------------------------------------------------------------------------ bond-resolved weights (COOP / COHP)
 // The contraction of one member (an edge or an on-site block) that bond_weights_kernel and kgrad_elements_kernel share, for the wave's 16 columns (column
@@ -398,7 +387,6 @@ template <int NT>
 __device__ __forceinline__ void member_contract(const float* __restrict__ X, const int32_t* __restrict__ ri, const int32_t* __restrict__ rj, int oi, int oj,
                                                 const float2* __restrict__ cb, const float2* __restrict__ ck, int nao, int M, int sl, int kq, float& pr_out,
                                                 float& pi_out) {
-    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
     int ra[NT];                                            // rank of this lane's A row a = 16 t + sl, or -1
     f32x4 tr[NT], ti[NT];
 #pragma unroll
@@ -412,7 +400,7 @@ __device__ __forceinline__ void member_contract(const float* __restrict__ X, con
         const int b = b0 + kq;
         int rb = rj[b < nao ? b : 0];
         rb = b < nao ? rb : -1;
-        float2 cj = ck[clampi(oj + rb, M)];
+        float2 cj = ck[hg_clampi(oj + rb, M)];
         cj = rb >= 0 ? cj : make_float2(0.f, 0.f);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -431,7 +419,7 @@ __device__ __forceinline__ void member_contract(const float* __restrict__ X, con
             const int a = 16 * t + 4 * kq + r;
             int rr = ri[a < nao ? a : 0];
             rr = a < nao ? rr : -1;
-            float2 ci = cb[clampi(oi + rr, M)];
+            float2 ci = cb[hg_clampi(oi + rr, M)];
             ci = rr >= 0 ? ci : make_float2(0.f, 0.f);
             pr = fmaf(ci.y, ti[t][r], fmaf(ci.x, tr[t][r], pr));
             pi = fmaf(-ci.y, tr[t][r], fmaf(ci.x, ti[t][r], pi));
@@ -446,7 +434,7 @@ __device__ __forceinline__ void member_contract(const float* __restrict__ X, con
 // One workgroup owns one (tile of 16 states, group); the group's members -- its edges in the order of eidx, then its atoms in the order of aidx -- are
 // dealt to the 4 waves in contiguous quarters.  Per member a wave forms c_i^+ X c_j for its 16 states with member_contract (above: two real GEMMs on
 // v_mfma_f32_16x16x4_f32 over the nao x nao block as it lies in the row, missing orbitals and tails by predication, so rectangular blocks need no padded
-// input), the phase (k . shift and sincos in double, rounded once, as hk_pairs_kernel) turns the
+// input), the phase (hg_edge_phase) turns the
 // complex sum into t_e, and the member is added to the wave's running sum.  The waves' sums are added through LDS as ((w0 + w1) + w2) + w3: one owner per
 // output element, a fixed order, no atomics.  The extra workgroups g = G write column 0 (= wk) and the pad columns (= 0); an empty group writes 0.  A state
 // row past ns repeats row ns - 1 and is not stored; the phase is per state, so the states of a tile may belong to different k-points, and a row of W does
@@ -471,11 +459,10 @@ __global__ __launch_bounds__(256) void bond_weights_kernel(const float2* __restr
         }
         return;
     }
-    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
     const int sl = lane & 15, kq = lane >> 4;
     const int sc = s0 + sl < ns ? s0 + sl : ns - 1;
     const float2* __restrict__ c = Cm + (int64_t)sc * M;
-    const int kp = clampi(kidx[sc], nk);
+    const int kp = hg_clampi(kidx[sc], nk);
     const double kx = kvec[3 * kp], ky = kvec[3 * kp + 1], kz = kvec[3 * kp + 2];
     const int e0 = eptr[g], a0 = aptr[g];
     const int ne = E > 0 && eptr[g + 1] > e0 ? eptr[g + 1] - e0 : 0, na = aptr[g + 1] > a0 ? aptr[g + 1] - a0 : 0;
@@ -487,18 +474,14 @@ __global__ __launch_bounds__(256) void bond_weights_kernel(const float2* __restr
         const bool edge = m < ne;
         int i, j;
         const float* __restrict__ X;
-        float cf = 1.f, sf = 0.f;
+        float2 ph = make_float2(1.f, 0.f);
         if (edge) {
-            const int e = clampi(eidx[e0 + m], E);
-            i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+            const int e = hg_clampi(eidx[e0 + m], E);
+            i = hg_clampi(erow[e], n_atoms), j = hg_clampi(ecol[e], n_atoms);
             X = X_off + (int64_t)e * nao2;
-            // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
-            const double ph = 6.283185307179586 * (kx * shift[3 * (int64_t)e] + ky * shift[3 * (int64_t)e + 1] + kz * shift[3 * (int64_t)e + 2]);
-            double sd, cd;
-            sincos(ph, &sd, &cd);
-            cf = (float)cd, sf = (float)sd;
+            ph = hg_edge_phase(kx, ky, kz, shift[3 * (int64_t)e], shift[3 * (int64_t)e + 1], shift[3 * (int64_t)e + 2]);
         } else {
-            i = j = clampi(aidx[a0 + (m - ne)], n_atoms);
+            i = j = hg_clampi(aidx[a0 + (m - ne)], n_atoms);
             X = X_on + (int64_t)i * nao2;
         }
         const int32_t* __restrict__ ri = orank + (int64_t)i * nao;
@@ -506,7 +489,7 @@ __global__ __launch_bounds__(256) void bond_weights_kernel(const float2* __restr
         const int oi = ooff[i], oj = ooff[j];
         float pr, pi;
         member_contract<NT>(X, ri, rj, oi, oj, c, c, nao, M, sl, kq, pr, pi);
-        sum += fmaf(cf, pr, -(sf * pi));                       // Re(phase * sum); an on-site member has phase 1
+        sum += fmaf(ph.x, pr, -(ph.y * pi));                     // Re(phase * sum); an on-site member has phase 1
     }
     if (kq == 0) part[wave][sl] = sum;
     __syncthreads();
@@ -529,13 +512,8 @@ extern "C" int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t*
     if (!C || !kidx || !kvec || !X_on || !orank || !ooff || !eptr || !aptr || !wk || !W || (n_edges > 0 && (!X_off || !erow || !ecol || !shift)))
         return hg_fail(-2, "hg_bond_weights: null pointer");
     const dim3 grid((unsigned)(ntile * ((int64_t)G + 1)));
-#define HG_BOND_LAUNCH(NT_)                                                                                                                               \
-    bond_weights_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, kidx, kvec, nk, X_on, X_off, erow, ecol, shift, (int)n_edges, \
-                                                                     n_atoms, nao, orank, ooff, eptr, eidx, aptr, aidx, G, Gp, (int)ntile, wk, W)
-    if (nao <= 16) HG_BOND_LAUNCH(1);
-    else if (nao <= 32) HG_BOND_LAUNCH(2);
-    else HG_BOND_LAUNCH(3);
-#undef HG_BOND_LAUNCH
+    HG_NT_LAUNCH(bond_weights_kernel, nao, grid, stream, (const float2*)C, (int)ns, M, kidx, kvec, nk, X_on, X_off, erow, ecol, shift, (int)n_edges, n_atoms, nao, orank, ooff,
+                 eptr, eidx, aptr, aidx, G, Gp, (int)ntile, wk, W);
     return hg_check_launch("hg_bond_weights");
 }
 
@@ -547,7 +525,7 @@ extern "C" int hg_bond_weights(const float* C, int64_t ns, int M, const int32_t*
 // accumulators): lane l holds A[r_a = 16 t + (l & 15)][state l >> 4] = f_s (x, y) of C[s][ooff[i] + r_a] and B[state l >> 4][r_b = 16 t + (l & 15)] =
 // (x', y') = exp(i theta) C[s][ooff[j] + r_b] -- the column operand is rotated once per loaded element, so that Re(phase conj(c_a) c_b) = x_a x'_b + y_a y'_b is
 // two real MFMA chains per tile instead of four; 16 lanes read 128 contiguous bytes of a row of C.  cos / sin of theta = 2 pi k . shift are formed once per
-// (k-point, member) in a prologue (k . shift and sincos in double, rounded once, as hk_pairs_kernel) into a table in LDS of the first DR_KCAP k-points; a
+// (k-point, member) in a prologue (hg_edge_phase) into a table in LDS of the first DR_KCAP k-points; a
 // state whose k-point lies beyond the table forms its own (the slow path of a very large k-list).  Ranks past n_i / n_j and state slots past ns contribute
 // operands of 0 (their loads are redirected into range).  The waves' partial tiles go to LDS; the epilogue walks the nao x nao row as it lies in memory
 // (coalesced), maps (a, b) to its ranks and adds the four partials as ((w0 + w1) + w2) + w3: one owner per element, a fixed order, no atomics.  accumulate
@@ -565,26 +543,20 @@ __global__ __launch_bounds__(256) void density_rows_kernel(const float2* __restr
     __shared__ float2 ptab[DR_KCAP];
     __shared__ int rki[48], rkj[48];                           // rank of orbital a of the row / column atom, or -1
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sl = lane & 15, kq = lane >> 4;
-    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
     const bool edge = (int)blockIdx.x < E;                     // (block-uniform)
     int i, j;
     float* __restrict__ out;
     double sx = 0.0, sy = 0.0, sz = 0.0;
     if (edge) {
         const int64_t e = blockIdx.x;
-        i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+        i = hg_clampi(erow[e], n_atoms), j = hg_clampi(ecol[e], n_atoms);
         out = P_off + e * nao * nao;
         sx = shift[3 * e], sy = shift[3 * e + 1], sz = shift[3 * e + 2];
     } else {
         i = j = (int)blockIdx.x - E;
         out = P_on + (int64_t)i * nao * nao;
     }
-    auto phase = [&](int kp) {                                 // |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
-        const double ph = 6.283185307179586 * ((double)kvec[3 * kp] * sx + (double)kvec[3 * kp + 1] * sy + (double)kvec[3 * kp + 2] * sz);
-        double sd, cd;
-        sincos(ph, &sd, &cd);
-        return make_float2((float)cd, (float)sd);
-    };
+    auto phase = [&](int kp) { return hg_edge_phase(kvec[3 * kp], kvec[3 * kp + 1], kvec[3 * kp + 2], sx, sy, sz); };
     if ((int)threadIdx.x < nao) {
         const int a = threadIdx.x, ra = orank[(int64_t)i * nao + a], rb = orank[(int64_t)j * nao + a];
         rki[a] = ra >= 0 && ra < 16 * NT ? ra : -1;
@@ -601,7 +573,7 @@ __global__ __launch_bounds__(256) void density_rows_kernel(const float2* __restr
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         va[t] = 16 * t + sl < ni, vb[t] = 16 * t + sl < nj;
-        ca[t] = clampi(oi + (va[t] ? 16 * t + sl : 0), M), cb[t] = clampi(oj + (vb[t] ? 16 * t + sl : 0), M);
+        ca[t] = hg_clampi(oi + (va[t] ? 16 * t + sl : 0), M), cb[t] = hg_clampi(oj + (vb[t] ? 16 * t + sl : 0), M);
     }
     const int nsteps = (ns + 3) >> 2, chunk = (nsteps + 3) >> 2;
     const int st0 = wave * chunk, st1 = st0 + chunk < nsteps ? st0 + chunk : nsteps;
@@ -620,7 +592,7 @@ __global__ __launch_bounds__(256) void density_rows_kernel(const float2* __restr
         for (int t = 0; t < NT; ++t) xa[t] = c[ca[t]], xb[t] = c[cb[t]];
         ph = make_float2(1.f, 0.f);
         if (edge) {
-            const int kp = clampi(kidx[s], nk);
+            const int kp = hg_clampi(kidx[s], nk);
             if (kp < DR_KCAP) ph = ptab[kp]; else ph = phase(kp);
         }
     };
@@ -689,13 +661,8 @@ extern "C" int hg_density_rows(const float* C, int64_t ns, int M, const int32_t*
         return hg_fail(-2, "hg_density_rows: null pointer");
     if (ns == 0 && accumulate) return 0;                       // nothing to add; without accumulate the launch writes the zero rows
     const dim3 grid((unsigned)(n_edges + n_atoms));
-#define HG_DENSITY_LAUNCH(NT_)                                                                                                                            \
-    density_rows_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, kidx, kvec, nk, f, erow, ecol, shift, (int)n_edges, n_atoms, \
-                                                                     nao, orank, ooff, accumulate ? 1 : 0, P_on, P_off)
-    if (nao <= 16) HG_DENSITY_LAUNCH(1);
-    else if (nao <= 32) HG_DENSITY_LAUNCH(2);
-    else HG_DENSITY_LAUNCH(3);
-#undef HG_DENSITY_LAUNCH
+    HG_NT_LAUNCH(density_rows_kernel, nao, grid, stream, (const float2*)C, (int)ns, M, kidx, kvec, nk, f, erow, ecol, shift, (int)n_edges, n_atoms, nao, orank, ooff,
+                 accumulate ? 1 : 0, P_on, P_off);
     return hg_check_launch("hg_density_rows");
 }
 
@@ -704,7 +671,7 @@ extern "C" int hg_density_rows(const float* C, int64_t ns, int M, const int32_t*
 // state ket_p, (i, j) = (erow[e], ecol[e]) and mu(i, a) = ooff[i] + orank[i][a] as above: the element <bra| dX(k)/dk_alpha |ket> of the k-derivative of the
 // assembled matrix (its on-site blocks do not depend on k), without the M x M matrix.  The per-edge contraction is member_contract, the one of bond_weights_kernel, with two
 // rows of C: T = X C_ket as two real GEMMs on v_mfma_f32_16x16x4_f32 (row tiles of 16 orbitals, steps of 4, tails and missing orbitals by predication),
-// conj(C_bra) . T over the lane's rows in the C/D layout, two shuffles, then the phase (k . shift and sincos in double, rounded once) as a complex product
+// conj(C_bra) . T over the lane's rows in the C/D layout, two shuffles, then the phase (hg_edge_phase) as a complex product
 // z_e, and per Cartesian component the running sums Re += -rvec z.im, Im += rvec z.re (one fused multiply-add each: a zero column of rvec gives exactly 0).
 // The single "group" is all E edges, so the edges are split: one workgroup owns one (tile of 16 pairs, chunk of hg_kgrad_chunk_edges(E) consecutive
 // edges); the chunk is dealt to the 4 waves in contiguous quarters, the waves' sums are added through LDS as ((w0 + w1) + w2) + w3 and stored to
@@ -723,13 +690,12 @@ __global__ __launch_bounds__(256) void kgrad_elements_kernel(const float2* __res
     __shared__ float part[4][6][16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ch = blockIdx.x / ntile, p0 = 16 * (blockIdx.x - ch * ntile);
-    auto clampi = [](int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; };
     const int sl = lane & 15, kq = lane >> 4;
     const int pc = p0 + sl < n_pairs ? p0 + sl : n_pairs - 1;
-    const int sk = clampi(ket[pc], ns), sb = clampi(bra[pc], ns);
+    const int sk = hg_clampi(ket[pc], ns), sb = hg_clampi(bra[pc], ns);
     const float2* __restrict__ ck = Cm + (int64_t)sk * M;
     const float2* __restrict__ cb = Cm + (int64_t)sb * M;
-    const int kp = clampi(kidx[sk], nk);
+    const int kp = hg_clampi(kidx[sk], nk);
     const double kx = kvec[3 * kp], ky = kvec[3 * kp + 1], kz = kvec[3 * kp + 2];
     const int eb = ch * chunk, ee = eb + chunk < E ? eb + chunk : E;
     const int quarter = (ee - eb + 3) >> 2;
@@ -737,19 +703,15 @@ __global__ __launch_bounds__(256) void kgrad_elements_kernel(const float2* __res
     const int nao2 = nao * nao;
     float ar[3] = {0.f, 0.f, 0.f}, ai[3] = {0.f, 0.f, 0.f};
     for (int e = m0; e < m1; ++e) {                            // (wave-uniform bounds and edge: every lane reaches every MFMA and shuffle)
-        const int i = clampi(erow[e], n_atoms), j = clampi(ecol[e], n_atoms);
+        const int i = hg_clampi(erow[e], n_atoms), j = hg_clampi(ecol[e], n_atoms);
         const float* __restrict__ X = X_off + (int64_t)e * nao2;
-        // phase in double: |k . shift| reaches tens of turns for long bonds, and sincosf loses the fraction
-        const double ph = 6.283185307179586 * (kx * shift[3 * (int64_t)e] + ky * shift[3 * (int64_t)e + 1] + kz * shift[3 * (int64_t)e + 2]);
-        double sd, cd;
-        sincos(ph, &sd, &cd);
-        const float cf = (float)cd, sf = (float)sd;
+        const float2 ph = hg_edge_phase(kx, ky, kz, shift[3 * (int64_t)e], shift[3 * (int64_t)e + 1], shift[3 * (int64_t)e + 2]);
         const int32_t* __restrict__ ri = orank + (int64_t)i * nao;
         const int32_t* __restrict__ rj = orank + (int64_t)j * nao;
         const int oi = ooff[i], oj = ooff[j];
         float pr, pi;
         member_contract<NT>(X, ri, rj, oi, oj, cb, ck, nao, M, sl, kq, pr, pi);
-        const float zr = fmaf(cf, pr, -(sf * pi)), zi = fmaf(cf, pi, sf * pr);      // z = phase * sum
+        const float zr = fmaf(ph.x, pr, -(ph.y * pi)), zi = fmaf(ph.x, pi, ph.y * pr);      // z = phase * sum
 #pragma unroll
         for (int al = 0; al < 3; ++al) {                       // i r z = -r z.im + i r z.re
             const float r = rvec[3 * (int64_t)e + al];
@@ -793,14 +755,8 @@ extern "C" int hg_kgrad_elements(const float* C, int64_t ns, int M, const int32_
     if (nchunk > 0) {
         const dim3 grid((unsigned)(ntile * nchunk));
         float* dst = nchunk > 1 ? part : out;
-#define HG_KGRAD_LAUNCH(NT_)                                                                                                                              \
-    kgrad_elements_kernel<NT_><<<grid, 256, 0, (hipStream_t)stream>>>((const float2*)C, (int)ns, M, bra, ket, (int)n_pairs, kidx, kvec, nk, X_off, erow, ecol, \
-                                                                       shift, rvec, (int)n_edges, n_atoms, nao, orank, ooff, (int)ntile,                  \
-                                                                       (int)hg_kgrad_chunk_edges(n_edges), dst)
-        if (nao <= 16) HG_KGRAD_LAUNCH(1);
-        else if (nao <= 32) HG_KGRAD_LAUNCH(2);
-        else HG_KGRAD_LAUNCH(3);
-#undef HG_KGRAD_LAUNCH
+        HG_NT_LAUNCH(kgrad_elements_kernel, nao, grid, stream, (const float2*)C, (int)ns, M, bra, ket, (int)n_pairs, kidx, kvec, nk, X_off, erow, ecol, shift, rvec, (int)n_edges,
+                     n_atoms, nao, orank, ooff, (int)ntile, (int)hg_kgrad_chunk_edges(n_edges), dst);
         if (nchunk == 1) return hg_check_launch("hg_kgrad_elements");
     }
     const int64_t n = 6 * n_pairs;

@@ -38,6 +38,8 @@ import numpy as np
 import torch
 
 from . import dos, ops
+from .bonds import group_tensors
+from .kspace import edge_phases, padded_rows
 
 
 def occupations(eps, mu, sigma, deg=2):
@@ -54,13 +56,11 @@ def _density_rows_torch(C, kidx, kvec, f, erow, ecol, shift, orank, ooff, out=No
     """ops.density_rows in torch ops, in the precision of C (complex64 or complex128): the rows of C gathered per atom into the nao-padded layout (0 where the
     atom lacks the orbital), the row operand scaled by f, then per chunk of edges the column operand times the phase (k . shift in double, rounded once) and
     two real einsums over the states"""
-    ns, M = C.shape
+    ns = int(C.shape[0])
     N, nao = orank.shape
     E = int(erow.shape[0])
     rdt = C.real.dtype
-    have = orank >= 0
-    comp = torch.where(have, ooff[:, None] + orank, torch.full_like(orank, M)).long()                # [N, nao]; M: the appended zero column
-    CA = torch.cat([C, C.new_zeros(ns, 1)], 1)[:, comp]                                               # [ns, N, nao]
+    CA, _ = padded_rows(C, orank, ooff)                                                               # [ns, N, nao]
     fx, fy = CA.real * f.to(rdt)[:, None, None], CA.imag * f.to(rdt)[:, None, None]
     P_on = (torch.einsum("sia,sib->iab", fx, CA.real) + torch.einsum("sia,sib->iab", fy, CA.imag)).reshape(N, nao * nao)
     P_off = torch.empty(E, nao * nao, device=C.device, dtype=rdt)
@@ -68,8 +68,7 @@ def _density_rows_torch(C, kidx, kvec, f, erow, ecol, shift, orank, ooff, out=No
     kd = kvec.double()[kidx.long()]                                                                   # [ns, 3]
     for q0 in range(0, E, step):
         i, j = erow[q0:q0 + step].long(), ecol[q0:q0 + step].long()
-        ang = 2.0 * np.pi * (kd @ shift[q0:q0 + step].double().T)                                    # [ns, members]
-        B = torch.complex(torch.cos(ang).to(rdt), torch.sin(ang).to(rdt))[:, :, None] * CA[:, j]
+        B = edge_phases(kd, shift[q0:q0 + step], rdt)[:, :, None] * CA[:, j]                          # [ns, members, nao]
         P_off[q0:q0 + step] = (torch.einsum("sea,seb->eab", fx[:, i], B.real) + torch.einsum("sea,seb->eab", fy[:, i], B.imag)).reshape(-1, nao * nao)
     if out is None:
         return P_on, P_off
@@ -131,7 +130,7 @@ def bond_populations(P_on, P_off, X_on, X_off, groups):
     Over groups that hold every edge and every atom exactly once the total is sum_s f_s (overlap rows, S-normalised states) / sum_s f_s eps_s (Hamiltonian
     rows).  Fixed-order sums."""
     dev = P_on.device
-    eptr, eidx, aptr, aidx = (g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, dtype=np.int32)).to(dev) for g in groups[:4])
+    eptr, eidx, aptr, aidx = group_tensors(groups, dev)
     G = int(eptr.shape[0]) - 1
     if G < 0 or int(aptr.shape[0]) != G + 1:
         raise ValueError(f"bond_populations: eptr and aptr must both be [G + 1], got {tuple(eptr.shape)}, {tuple(aptr.shape)}")

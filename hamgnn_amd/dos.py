@@ -47,6 +47,21 @@ PAD_SIGMAS = 8.0            # erange_eV=None: the whole spectrum +- 8 sigma
 
 
 # ------------------------------------------------------------------------------------------------ the k-grid
+def _fold_time_reversal(k):
+    """the k / -k folding of a full grid k [n, 3]: yields, per point in grid order, (r, True) -- the point is kept as row r of the folded list -- or
+    (r, False) -- it is the partner (-k modulo a reciprocal lattice vector) of the kept row r.  The first of a pair in grid order is kept."""
+    key = lambda v: tuple(int(t) for t in np.rint((v - np.floor(v + 1e-12)) * 2 ** 40) % 2 ** 40)      # k modulo 1 on a 2^-40 lattice
+    seen, kept = {}, 0
+    for i in range(k.shape[0]):
+        me, partner = key(k[i]), key(-k[i])
+        if partner in seen and partner != me:
+            yield seen[partner], False
+            continue
+        seen[me] = kept
+        yield kept, True
+        kept += 1
+
+
 def monkhorst_pack(grid, shift=(0, 0, 0), time_reversal: bool = True):
     """(k_reduced [nk, 3], weights [nk]): the Gamma-centred n1 x n2 x n3 grid k = ((i1 + s1) / n1, (i2 + s2) / n2, (i3 + s3) / n3) folded into
     (-1/2, 1/2], weights summing to 1.  With `time_reversal`, k and -k (modulo a reciprocal lattice vector) are one point of doubled weight --
@@ -62,17 +77,10 @@ def monkhorst_pack(grid, shift=(0, 0, 0), time_reversal: bool = True):
     w = np.full(k.shape[0], 1.0 / k.shape[0])
     if not time_reversal:
         return k, w
-    key = lambda v: tuple(int(t) for t in np.rint((v - np.floor(v + 1e-12)) * 2 ** 40) % 2 ** 40)      # k modulo 1 on a 2^-40 lattice
-    seen, keep, weight = {}, [], []
-    for i in range(k.shape[0]):
-        me, partner = key(k[i]), key(-k[i])
-        if partner in seen and partner != me:
-            weight[seen[partner]] += w[i]
-            continue
-        seen[me] = len(keep)
-        keep.append(i)
-        weight.append(w[i])
-    return k[keep], np.asarray(weight)
+    fold = list(_fold_time_reversal(k))
+    keep = [i for i, (_, kept) in enumerate(fold) if kept]
+    weight = np.bincount([r for r, _ in fold], weights=w)      # a row's weight: the kept point's, then its partner's
+    return k[keep], weight
 
 
 def monkhorst_pack_map(grid, shift=(0, 0, 0), time_reversal: bool = True) -> np.ndarray:
@@ -81,16 +89,7 @@ def monkhorst_pack_map(grid, shift=(0, 0, 0), time_reversal: bool = True) -> np.
     k, _ = monkhorst_pack(grid, shift, time_reversal=False)
     if not time_reversal:
         return np.arange(k.shape[0], dtype=np.int32)
-    key = lambda v: tuple(int(t) for t in np.rint((v - np.floor(v + 1e-12)) * 2 ** 40) % 2 ** 40)
-    seen, out, kept = {}, np.empty(k.shape[0], dtype=np.int32), 0
-    for i in range(k.shape[0]):
-        me, partner = key(k[i]), key(-k[i])
-        if partner in seen and partner != me:
-            out[i] = seen[partner]
-            continue
-        seen[me] = out[i] = kept
-        kept += 1
-    return out
+    return np.asarray([r for r, _ in _fold_time_reversal(k)], dtype=np.int32)
 
 
 _CORNERS = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]])           # the starting corners of the four main diagonals of a grid cell
@@ -371,12 +370,9 @@ def tetra_states(eps, W, tet, E0, dE, ne, D=None, accumulate=False):
 
 
 # ------------------------------------------------------------------------------------------------ host helpers
-def fermi_level(eps, w, nel, sigma, deg):
-    """the level mu at which deg * sum_s w_s erfc((eps_s - mu) / (sigma sqrt 2)) / 2 = nel; bisection in fp64 on the host.  Where the count is flat
-    (a gap much wider than sigma) every level of the plateau holds nel to rounding: the middle of the plateau is returned."""
-    eps_t, w_t = torch.from_numpy(np.asarray(eps, dtype=np.float64)), torch.from_numpy(np.asarray(w, dtype=np.float64))
-    count = lambda mu: deg * float((w_t * 0.5 * torch.erfc((eps_t - mu) / (sigma * math.sqrt(2.0)))).sum())
-    lo0, hi0 = float(eps_t.min()) - 10.0 * sigma, float(eps_t.max()) + 10.0 * sigma
+def _plateau_level(count, lo0, hi0, nel):
+    """the level in [lo0, hi0] at which the non-decreasing count(mu) = nel, by bisection in fp64.  Where the count is flat every level of the plateau
+    holds nel to the tolerance 1e-12 max(1, nel): the mean of the plateau's two ends is returned."""
     tol = 1e-12 * max(1.0, nel)
     if not count(lo0) - tol <= nel <= count(hi0) + tol:
         raise ValueError(f"{nel} electrons do not fit {count(hi0):.3f} states")
@@ -393,6 +389,14 @@ def fermi_level(eps, w, nel, sigma, deg):
                 break
         return 0.5 * (lo + hi)
     return 0.5 * (edge(nel - tol, True) + edge(nel + tol, False))
+
+
+def fermi_level(eps, w, nel, sigma, deg):
+    """the level mu at which deg * sum_s w_s erfc((eps_s - mu) / (sigma sqrt 2)) / 2 = nel; bisection in fp64 on the host.  Where the count is flat
+    (a gap much wider than sigma) every level of the plateau holds nel to rounding: the middle of the plateau is returned."""
+    eps_t, w_t = torch.from_numpy(np.asarray(eps, dtype=np.float64)), torch.from_numpy(np.asarray(w, dtype=np.float64))
+    count = lambda mu: deg * float((w_t * 0.5 * torch.erfc((eps_t - mu) / (sigma * math.sqrt(2.0)))).sum())
+    return _plateau_level(count, float(eps_t.min()) - 10.0 * sigma, float(eps_t.max()) + 10.0 * sigma, nel)
 
 
 def fermi_level_tetra(eps, tet, nel, deg):
@@ -414,22 +418,7 @@ def fermi_level_tetra(eps, tet, nel, deg):
         return deg * float(np.where(mu >= e4, 1.0, np.where(mu <= e1, 0.0, n)).sum()) / tet.shape[0]
 
     lo0, hi0 = float(eps.min()), float(eps.max())
-    tol = 1e-12 * max(1.0, nel)
-    if not count(lo0) - tol <= nel <= count(hi0) + tol:
-        raise ValueError(f"{nel} electrons do not fit {count(hi0):.3f} states")
-
-    def edge(target, below):                                   # the first level whose count reaches (below) / exceeds (not below) the target
-        lo, hi = lo0, hi0
-        for _ in range(200):
-            mid = 0.5 * (lo + hi)
-            if (count(mid) < target) if below else (count(mid) <= target):
-                lo = mid
-            else:
-                hi = mid
-            if hi - lo <= 1e-13 * max(1.0, abs(mid)):
-                break
-        return 0.5 * (lo + hi)
-    mu = 0.5 * (edge(nel - tol, True) + edge(nel + tol, False))
+    mu, tol = _plateau_level(count, lo0, hi0, nel), 1e-12 * max(1.0, nel)      # (its tolerance on the count)
     # the count leaves a plateau like a cube, so the bisection finds its ends only to the cube root of tol: a plateau ends at eigenvalues, take those
     below, above = eps[eps <= mu], eps[eps >= mu]
     a, b = float(below.max()) if below.size else lo0, float(above.min()) if above.size else hi0

@@ -191,6 +191,21 @@ class CrystalTables:
         return torch.where(self.orank >= 0, self.ooff[:, None] + self.orank, torch.full_like(self.orank, -1)).long()
 
 
+def padded_rows(C, orank, ooff):
+    """(CA [ns, N, nao], have [N, nao]): the rows of C [ns, M] gathered per atom into the nao-padded layout, CA[s, i, a] = C[s, ooff[i] + orank[i][a]] and 0
+    where the atom lacks the orbital (have = orank >= 0): the torch paths of bonds.py, density.py and velocity.py start here"""
+    ns, M = C.shape
+    have = orank >= 0
+    comp = torch.where(have, ooff[:, None] + orank, torch.full_like(orank, M)).long()                # [N, nao]; M: the appended zero column
+    return torch.cat([C, C.new_zeros(ns, 1)], 1)[:, comp], have
+
+
+def edge_phases(k, shift, rdt):
+    """complex [n, m] of real dtype rdt: exp(2 pi i k . shift) of the k rows [n, 3] and the shifts [m, 3]; the angle in double, rounded once (as hg_edge_phase)"""
+    ang = 2.0 * np.pi * (k.double() @ shift.double().T)
+    return torch.complex(torch.cos(ang).to(rdt), torch.sin(ang).to(rdt))
+
+
 def assemble_k(on, off, tab, kvec):
     """[nk, M, M] complex64 of one crystal (the rows and edges of `tab`) from planar [.., nao^2] blocks of the batch"""
     return ops.hk_assemble(on[tab.n0:tab.n0 + tab.n].contiguous(), off[tab.e0:tab.e0 + tab.e].contiguous(), tab.shift, kvec.contiguous().float(),
@@ -220,8 +235,7 @@ def _assemble_k_adjoint_torch(G, tab, kvec):
     g_on = (Gon.real.sum(0) * ok_on).reshape(n, nao * nao)
     R, Cc = comp[tab.erow.long()], comp[tab.ecol.long()]
     ok = ((R[:, :, None] >= 0) & (Cc[:, None, :] >= 0)).to(rdt)
-    ph = 2.0 * math.pi * (kvec.to(torch.float64)[:, None, :] * tab.shift.to(torch.float64)[None, :, :]).sum(-1)  # [nk, e] in double (see the kernel)
-    cph = torch.complex(torch.cos(ph), -torch.sin(ph)).to(G.dtype)                               # conj(phase)
+    cph = edge_phases(kvec, tab.shift, torch.float64).conj().to(G.dtype)                         # [nk, e] conj(phase), formed in double (see the kernel)
     g_off = torch.zeros(e, nao, nao, device=G.device, dtype=rdt)
     for k0 in range(0, nk, 8):
         Ge = G[k0:k0 + 8][:, R.clamp(min=0)[:, :, None], Cc.clamp(min=0)[:, None, :]]          # [<=8, e, nao, nao]

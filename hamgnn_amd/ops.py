@@ -884,6 +884,17 @@ def mulliken_weights(C_, SC, perm, gptr, wk, Gp):
     return W
 
 
+def _dos_out(who, D, ne, Gp, accumulate, device):
+    """the D [ne, Gp] fp32 that dos_broaden / dos_tetra write: the caller's, checked, or a new one (which accumulate cannot add to)"""
+    if D is None:
+        if accumulate:
+            raise ValueError(f"{who}: accumulate needs the D to add to")
+        return torch.empty(ne, Gp, device=device, dtype=torch.float32)
+    if tuple(D.shape) != (ne, Gp):
+        raise ValueError(f"{who}: D must be [{ne}, {Gp}], got {tuple(D.shape)}")
+    return D
+
+
 @_on_tensor_device
 def dos_broaden(eps, W, E0, dE, ne, sigma, D=None, accumulate=False):
     """D [ne, Gp] fp32 (+)= Gaussians of width sigma around the ASCENDING eps [ns], weighted by W [ns, Gp], on the grid E0 + j dE (see
@@ -891,12 +902,7 @@ def dos_broaden(eps, W, E0, dE, ne, sigma, D=None, accumulate=False):
     if W.dim() != 2 or tuple(eps.shape) != (W.shape[0],):
         raise ValueError(f"dos_broaden: W must be [ns, Gp] and eps [ns], got {tuple(W.shape)}, {tuple(eps.shape)}")
     ns, Gp = int(W.shape[0]), int(W.shape[1])
-    if D is None:
-        if accumulate:
-            raise ValueError("dos_broaden: accumulate needs the D to add to")
-        D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
-    elif tuple(D.shape) != (ne, Gp):
-        raise ValueError(f"dos_broaden: D must be [{ne}, {Gp}], got {tuple(D.shape)}")
+    D = _dos_out("dos_broaden", D, ne, Gp, accumulate, W.device)
     call("hg_dos_broaden", eps, W, ns, Gp, E0, dE, ne, sigma, bool(accumulate), D)
     return D
 
@@ -919,12 +925,7 @@ def dos_tetra(eps, W, tet, kt, band_lo, band_hi, E0, dE, ne, mode=0, D=None, acc
                          f"kt_tet {tuple(kt_tet.shape)}, kt_corner {tuple(kt_corner.shape)}, band_lo {tuple(band_lo.shape)}, band_hi {tuple(band_hi.shape)}")
     if Gp < 1 or mode not in (0, 1):
         raise ValueError(f"dos_tetra: Gp = {Gp} must be at least 1 and mode = {mode!r} 0 (DOS) or 1 (number of states)")
-    if D is None:
-        if accumulate:
-            raise ValueError("dos_tetra: accumulate needs the D to add to")
-        D = torch.empty(ne, Gp, device=W.device, dtype=torch.float32)
-    elif tuple(D.shape) != (ne, Gp):
-        raise ValueError(f"dos_tetra: D must be [{ne}, {Gp}], got {tuple(D.shape)}")
+    D = _dos_out("dos_tetra", D, ne, Gp, accumulate, W.device)
     call("hg_dos_tetra", eps, W, nk, nb, Gp, tet, nt, kt_ptr, kt_tet, kt_corner, band_lo, band_hi, E0, dE, ne, mode, bool(accumulate), D)
     return D
 

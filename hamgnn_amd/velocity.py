@@ -39,13 +39,11 @@ import numpy as np
 import torch
 
 from . import dos, ops
+from .bonds import _np
+from .kspace import edge_phases, padded_rows
 
 PAIRS = ("xx", "yy", "zz", "yz", "xz", "xy")                  # the column order of transport_weights
 _PAIR_IDX = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
-
-
-def _np(a, dtype):
-    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
 
 
 # ------------------------------------------------------------------------------------------------ edge vectors (host)
@@ -77,13 +75,10 @@ def _kgrad_elements_torch(C, bra, ket, kidx, kvec, X_off, erow, ecol, shift, rve
     """ops.kgrad_elements in torch ops, in the precision of C (complex64 or complex128): the rows of C gathered per atom into the nao-padded layout (0 where
     the atom lacks the orbital), then per chunk of edges one einsum X c_ket, the dot with conj(c_bra), the phase (k . shift in double, rounded once) and
     one matmul with i rvec"""
-    ns, M = C.shape
     N, nao = orank.shape
     E, npair = int(erow.shape[0]), int(ket.shape[0])
     rdt = C.real.dtype
-    have = orank >= 0
-    comp = torch.where(have, ooff[:, None] + orank, torch.full_like(orank, M)).long()                # [N, nao]; M: the appended zero column
-    CA = torch.cat([C, C.new_zeros(ns, 1)], 1)[:, comp]                                               # [ns, N, nao]
+    CA, have = padded_rows(C, orank, ooff)                                                            # [ns, N, nao]
     hv = have.to(rdt)
     b, k = bra.long()[:, None], ket.long()[:, None]
     kd = kvec.double()[kidx.long()[ket.long()]]                                                       # [np, 3]
@@ -94,8 +89,7 @@ def _kgrad_elements_torch(C, bra, ket, kidx, kvec, X_off, erow, ecol, shift, rve
         X = X_off[q0:q0 + step].to(rdt).reshape(-1, nao, nao) * hv[i][:, :, None] * hv[j][:, None, :]
         T = torch.einsum("eab,peb->pea", X.to(C.dtype), CA[k, j[None, :]])
         p = (CA[b, i[None, :]].conj() * T).sum(-1)                                                    # [np, edges]
-        ang = 2.0 * np.pi * (kd @ shift[q0:q0 + step].double().T)
-        z = torch.complex(torch.cos(ang).to(rdt), torch.sin(ang).to(rdt)) * p
+        z = edge_phases(kd, shift[q0:q0 + step], rdt) * p
         out += torch.complex(-z.imag, z.real) @ rvec[q0:q0 + step].to(C.dtype)                        # i z R
     return out
 
